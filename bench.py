@@ -1,10 +1,15 @@
 """Training-step benchmark: 64x64 ImageNet SMMD (SNResNet G/D), batch 64 per GPU.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: one rank per GPU over RCCL.  Started without a launcher, the
     process starts `torch.distributed.run --nproc-per-node N bench.py ...` as
     a child before touching the GPU and exits with its code; started by a
     launcher, --gpus must equal WORLD_SIZE)
+
+A plain run does what the headline needs and nothing else: it primes, warms
+up, times the K steps and prints the result line.  --full adds every other
+measurement (items 4-6 below and the reference schedule's half of item 1).
+--dump-outputs DIR writes what the last timed step handed back (dump_outputs).
 
 A step is one optimizer update of the reference schedule (5 critic updates,
 then 1 generator update; gan/core/model.py:470-478) on a synthetic batch of
@@ -14,13 +19,21 @@ timed region).  Multi-GPU uses the all-gather ('global') MMD mode: every rank
 sees the full (N*64) x (N*64) pairwise kernel (weak scaling).
 
 Order of the run:
-  1. prime (untimed): one critic and one generator update in each schedule
-     (lean and reference), so every distinct autograd graph -- and every
-     MIOpen kernel it needs -- is built before anything is timed;
+  1. prime (untimed): one critic and one generator update in the lean
+     schedule (--full: and in the reference schedule), so every distinct
+     autograd graph -- and every MIOpen kernel it needs -- is built before
+     anything is timed; on one GPU with --graphs -1 (the default) the graphs
+     probe follows: two untimed 5D + 1G cycles eagerly and two as HIP-graph
+     replays, and the timed steps replay graphs only when that was >= 5 %
+     faster.  The probe chooses how the headline's steps run, so it is part
+     of a plain run too (36 untimed steps, counted in `prime_steps`); --graphs
+     0 or 1 fixes the choice and skips it;
   2. W warmup steps, then the schedule is re-aligned to the start of a
      5D + 1G cycle;
   3. EXACTLY K timed steps (no events, no per-call instrumentation inside);
-     the line reports how many were critic / generator updates;
+     the line reports how many were critic / generator updates; then the
+     outputs of the last one are written when --dump-outputs is given;
+  --full only:
   4. the reference schedule (both gradient sets every step, model.py:514);
   5. a separate instrumented pass over whole cycles: HIP-event time of every
      libsmmd_hip entry point and of each D / G step (the `roofline`,
@@ -507,12 +520,68 @@ def step_flops(model, images):
             'flops_per_avg_step': (5 * per_img_d + per_img_g) * BATCH / 6}
 
 
+def step_rate(model, images, counts, ms_step, stamp):
+    """The `roofline_hot_path.step` block: step_flops over the timed region's
+    own mix of D and G steps (`counts`) and its step time, with the counter
+    figures of step_counters beside it."""
+    fl = step_flops(model, images)
+    fl_timed = (counts['D'] * fl['flops_per_D_step'] + counts['G'] * fl['flops_per_G_step']) \
+        / max(counts['D'] + counts['G'], 1)
+    tfs = fl_timed / (ms_step * 1e-3) / 1e12
+    return dict(fl, flops_per_timed_step=fl_timed,
+                literal_work_rate_tflops=round(tfs, 2),
+                literal_work_rate_over_fp32_peak=round(tfs / FP32_PEAK_TFS, 4),
+                fp32_peak_tflops=FP32_PEAK_TFS,
+                note='literal work rate = the reference\'s literal conv layers (no '
+                     'fold, direct-conv MAC count) per second of this run; the '
+                     'product runs Winograd and folded stride-2 convs, which execute '
+                     'fewer MACs, so this rate can exceed the peak and is not a '
+                     'utilisation; `counters` holds the executed-FLOP figures '
+                     '(rocprofv3, stamped with the library build they were measured on)',
+                counters=step_counters(ms_step, stamp))
+
+
 def run_steps(model, images, k, counts=None):
     for i in range(k):
         before = model.step
         model.train_step(images[i % len(images)])
         if counts is not None:
             counts['G' if model.step != before else 'D'] += 1
+
+
+DUMP_BUDGET = 60 * 1000 * 1000   # bytes over all the arrays of one --dump-outputs
+
+
+def dump_sample(a, cap):
+    """`a` flattened, whole when it has at most `cap` elements, else a fixed
+    sample of `cap`: the elements at sorted indices drawn without replacement
+    by numpy default_rng(0), the same for every array of that size."""
+    import numpy as np
+    a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+    if a.size <= cap:
+        return a
+    idx = np.sort(np.random.default_rng(0).choice(a.size, size=cap, replace=False))
+    return a[idx]
+
+
+def dump_outputs(model, out_dir):
+    """What the last timed step computed, as out_dir/<name>.npy (float32):
+    g_loss, d_loss and aux (the scaling statistics, when the loss has them) as
+    train_step handed them back (model.last), and what it left for the next
+    call: g_params and d_params, the generator's and the critic's parameters
+    after that step's update (each optimizer's flat buffer, parameters in
+    order).  The scalars are written whole; the two parameter vectors share
+    the rest of DUMP_BUDGET equally (dump_sample).  Returns {name: elements}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: model.last[k].detach().cpu().numpy() for k in ('g_loss', 'd_loss', 'aux')
+              if torch.is_tensor(model.last.get(k))}
+    cap = (DUMP_BUDGET // 4 - sum(a.size for a in arrays.values())) // 2
+    arrays['g_params'] = dump_sample(model.g_optim.flat_param.detach().cpu().numpy(), cap)
+    arrays['d_params'] = dump_sample(model.d_optim.flat_param.detach().cpu().numpy(), cap)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), np.asarray(a, dtype=np.float32))
+    return {name: int(np.asarray(a).size) for name, a in arrays.items()}
 
 
 def sync(world):
@@ -575,6 +644,30 @@ def launch_plan(gpus, env):
     return ('run', gpus)
 
 
+def run_parts(args, world=1, rank=0):
+    """Which parts of a run these arguments ask for.  The timed steps (and
+    what leads up to them: the lean schedule's priming, the graphs probe of
+    --graphs -1, the warmup) always run; every other measurement needs
+    --full and is then governed by its own option:
+      prime_schedules   the schedules primed before the warmup
+      ref_schedule      the reference schedule's timed leg
+      instrumented      the per-call HIP-event pass (roofline, hip_kernels)
+      step_flops        the step FLOP count (roofline_hot_path.step)
+      mmd_sweep         the MMD microbench
+      cpu_baseline      the CPU mirror (rank 0 of a one-GPU run)
+      dump_outputs      the last timed step's outputs written (rank 0)"""
+    full = bool(args.full)
+    return {
+        'prime_schedules': ('lean', 'reference') if full else ('lean',),
+        'ref_schedule': full and args.ref_schedule_steps > 0,
+        'instrumented': full and args.instrument_cycles > 0,
+        'step_flops': full,
+        'mmd_sweep': full and bool(args.mmd_sweep),
+        'cpu_baseline': full and rank == 0 and world == 1 and not args.no_cpu_baseline,
+        'dump_outputs': bool(args.dump_outputs) and rank == 0,
+    }
+
+
 def _free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -594,7 +687,7 @@ def spawn_ranks(n, argv):
     return subprocess.call(cmd)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--batch', type=int, default=64,
@@ -606,6 +699,14 @@ def main():
     ap.add_argument('--steps', type=int, default=60)
     ap.add_argument('--warmup', type=int, default=12)
     ap.add_argument('--dp-mode', default='global', choices=['global', 'tower'])
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also run every other measurement: the '
+                         'reference schedule, the instrumented pass (roofline, hip_kernels), '
+                         'the step FLOP count, the MMD microbench and the CPU baseline, each '
+                         'under its own option below; without --full none of them runs')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last one handed back and '
+                         'left behind as DIR/<name>.npy (float32; see dump_outputs)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--channels-last', type=int, default=0)
     ap.add_argument('--miopen-winograd', type=int, default=1,
@@ -633,7 +734,11 @@ def main():
                          '0: skip')
     ap.add_argument('--mmd-sweep', type=int, default=1,
                     help='1: SURVEY 8d MMD microbench grid; 2: four configs; 0: skip')
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main():
+    args = parse_args()
     global BATCH
     BATCH = args.batch
 
@@ -705,9 +810,12 @@ def main():
     log = (lambda *a: print('[bench]', *a, file=sys.stderr, flush=True)) if rank == 0 else \
         (lambda *a: None)
 
-    # 1. prime every autograd graph (and its MIOpen kernels) once, untimed
+    # 1. prime every autograd graph (and its MIOpen kernels) once, untimed;
+    # the reference schedule's only where it is measured (--full)
     tw = time.perf_counter()
-    for sched in ('lean', 'reference'):
+    parts = run_parts(args, world, rank)
+    schedules = parts['prime_schedules']
+    for sched in schedules:
         model.schedule = sched
         model.d_step(images[0])
         model.g_step(images[1])
@@ -748,7 +856,8 @@ def main():
         run_steps(model, images, 6)
     args.graphs = use_graphs
     sync(world)
-    log('primed D and G steps of both schedules in %.1f s' % (time.perf_counter() - tw))
+    log('primed D and G steps of %s in %.1f s' % (' and '.join(schedules),
+                                                  time.perf_counter() - tw))
 
     # 2. warmup, then align to the start of a 5 D + 1 G cycle
     model.step = 21          # steady state: 5 critic updates per generator update
@@ -770,11 +879,16 @@ def main():
     dt = max_over_ranks(time.perf_counter() - t0, world, dev)
     g_loss, d_loss = model.check_finite()
     log('timed %d steps: %.2f ms/step' % (args.steps, dt / args.steps * 1e3))
+    dumped = None
+    if parts['dump_outputs']:
+        dumped = dump_outputs(model, args.dump_outputs)
+        log('wrote %s to %s' % (', '.join('%s[%d]' % kv for kv in dumped.items()),
+                                args.dump_outputs))
 
     # 4. the reference schedule (both gradient sets every step, model.py:514)
     model.enable_graphs(False)      # the rest runs eagerly
     ref_sched = None
-    if args.ref_schedule_steps > 0:
+    if parts['ref_schedule']:
         model.schedule = 'reference'
         model.d_counter = model.g_counter = 0
         run_steps(model, images, 6)                       # one cycle
@@ -799,7 +913,7 @@ def main():
     from gan.core import _lib
     stamp = _lib.lib().smmd_source_hash().decode()     # the running library build
     kernels, step_ms, roofline, hot = {}, {}, None, {}
-    if args.instrument_cycles > 0:
+    if parts['instrumented']:
         tm, tb, step_ms, n_inst = instrumented_pass(model, images, args.instrument_cycles,
                                                     world, dev)
         m_all = BATCH * world
@@ -943,26 +1057,12 @@ def main():
                 'bound': 'latency at D = 1 (one launch per critic step)'}
         log('instrumented pass: %d steps' % n_inst)
 
-    fl = step_flops(model, images[0])
     ms_step = dt / args.steps * 1e3
-    # the timed region's own mix of D and G steps
-    fl_timed = (counts['D'] * fl['flops_per_D_step'] + counts['G'] * fl['flops_per_G_step']) \
-        / max(counts['D'] + counts['G'], 1)
-    tfs = fl_timed / (ms_step * 1e-3) / 1e12
-    hot['step'] = dict(fl, flops_per_timed_step=fl_timed,
-                       literal_work_rate_tflops=round(tfs, 2),
-                       literal_work_rate_over_fp32_peak=round(tfs / FP32_PEAK_TFS, 4),
-                       fp32_peak_tflops=FP32_PEAK_TFS,
-                       note='literal work rate = the reference\'s literal conv layers (no '
-                            'fold, direct-conv MAC count) per second of this run; the '
-                            'product runs Winograd and folded stride-2 convs, which execute '
-                            'fewer MACs, so this rate can exceed the peak and is not a '
-                            'utilisation; `counters` holds the executed-FLOP figures '
-                            '(rocprofv3, stamped with the library build they were measured on)',
-                       counters=step_counters(ms_step, stamp))
+    if parts['step_flops']:
+        hot['step'] = step_rate(model, images[0], counts, ms_step, stamp)
 
     sweep = None
-    if args.mmd_sweep:
+    if parts['mmd_sweep']:
         sweep = mmd_sweep(world, rank, dev, dist.group.WORLD if world > 1 else None,
                           quick=args.mmd_sweep == 2)
         hot['mmd_sweep_valu'] = [{'kernel': r['kernel'], 'N': r['N'], 'kernel_ms': r['kernel_ms'],
@@ -976,7 +1076,7 @@ def main():
         'n_gpus': world,
         'steps': args.steps,
         'warmup': args.warmup,
-        'prime_steps': 4 + (36 if graphs_probe else (6 if args.graphs else 0)),
+        'prime_steps': 2 * len(schedules) + (36 if graphs_probe else (6 if args.graphs else 0)),
         'd_steps': counts['D'],
         'g_steps': counts['G'],
         'ms_per_step': round(ms_step, 3),
@@ -1006,6 +1106,8 @@ def main():
         'schedule_reference': ref_sched,
         'mmd_sweep': sweep,
         'losses': {'g_loss': g_loss, 'd_loss': d_loss},
+        'full': bool(args.full),
+        'outputs': {'dir': args.dump_outputs, 'elements': dumped} if dumped else None,
     }
     if step_ms.get('D') and step_ms.get('G'):
         # from the instrumented pass (HIP events around every library call and
@@ -1015,7 +1117,7 @@ def main():
         result['instrumented_cycle_value'] = round(
             world * BATCH * 6 / ((5 * step_ms['D'] + step_ms['G']) * 1e-3), 2)
     result['whole_cycles_timed'] = (counts['G'] if counts['D'] == 5 * counts['G'] else None)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if parts['cpu_baseline']:
         try:
             result['cpu_baseline'] = cpu_baseline(args.cpu_steps)
         except Exception as e:   # report, never hide the GPU number

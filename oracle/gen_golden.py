@@ -69,7 +69,13 @@ def gen_sn():
 def main():
     os.makedirs(OUT, exist_ok=True)
     np.savez_compressed(os.path.join(OUT, 'mmd2_cases.npz'), **gen_mmd())
-    np.savez_compressed(os.path.join(OUT, 'sn_cases.npz'), **gen_sn())
+    # the two float64 matrices per case in files of their own: each file
+    # stays under 1 MiB
+    sn = gen_sn()
+    for name, suffix in (('sn_cases_weff.npz', '__Weff'), ('sn_cases_gw.npz', '__gW')):
+        np.savez_compressed(os.path.join(OUT, name),
+                            **{k: sn.pop(k) for k in sorted(sn) if k.endswith(suffix)})
+    np.savez_compressed(os.path.join(OUT, 'sn_cases.npz'), **sn)
     print('wrote', OUT)
 
 

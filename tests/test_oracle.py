@@ -179,6 +179,32 @@ def test_golden_sn_regression():
         np.testing.assert_allclose(u1, z[key + '__u1'], rtol=1e-12, atol=1e-15)
 
 
+def test_golden_sn_weight_and_backward_regression():
+    """W_eff and dL/dW of every SN case (sn_cases_weff.npz, sn_cases_gw.npz)
+    from the inputs in sn_cases.npz.  Each element is a float64 sum of up to
+    N + K products, whose order a BLAS may change: sqrt(N + K) eps ~ 6e-15 of
+    the array's scale at the largest case, so 1e-12 of the largest expected
+    magnitude as the absolute bound (and 1e-12 relative) leaves two orders.
+    The scale gradient gs is one sum of N K signed products (rounding
+    ~ sqrt(N K) eps |G W| / sigma ~ 1e-13 absolute at most): 1e-10 relative."""
+    z = np.load(os.path.join(GOLDEN, 'sn_cases.npz'))
+    weff = np.load(os.path.join(GOLDEN, 'sn_cases_weff.npz'))
+    gw = np.load(os.path.join(GOLDEN, 'sn_cases_gw.npz'))
+    keys = sorted({k.rsplit('__', 1)[0] for k in z.files})
+    assert sorted(weff.files) == [k + '__Weff' for k in keys]
+    assert sorted(gw.files) == [k + '__gW' for k in keys]
+    for key in keys:
+        W, s = z[key + '__W'], float(z[key + '__s'])
+        sigma, u1, v1 = O.spectral_norm_rows(W, z[key + '__u'])
+        want = weff[key + '__Weff']
+        np.testing.assert_allclose(W.astype(np.float64) / sigma * s, want, rtol=1e-12,
+                                   atol=1e-12 * np.abs(want).max())
+        gW, gs = O.sn_weight_backward(W, s, sigma, u1, v1, z[key + '__G'])
+        want = gw[key + '__gW']
+        np.testing.assert_allclose(gW, want, rtol=1e-12, atol=1e-12 * np.abs(want).max())
+        assert gs == pytest.approx(float(z[key + '__gs']), rel=1e-10)
+
+
 # ---- polynomial-kernel MMD (KID scorer / 3-sample scheduler) --------------
 def test_polynomial_kernel_matches_sklearn():
     """The reference calls sklearn's polynomial_kernel (compute_scores.py:237-239)."""
