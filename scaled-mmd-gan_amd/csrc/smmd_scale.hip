@@ -320,7 +320,7 @@ static_assert(sizeof(OptTable) + sizeof(SnAdamTable) + sizeof(AdamArgs) <= 4000,
 static AdamArgs adam_args(float *p, const float *g, float *m, float *v, const void *ws,
                           float gscale, float clip, double lr_t, float b1, float b2, float eps,
                           int vec) {
-    AdamArgs a;
+    AdamArgs a{};
     a.p = p;
     a.m = m;
     a.v = v;
@@ -453,7 +453,7 @@ smmd_status smmd_scaled_loss_bwd(const float *jac, int n_cols, int b, int b_tota
     int64_t blocks = (n_jac / 4 + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     if (blocks < 1) blocks = 1;
-    MmdBwdPart mp;
+    MmdBwdPart mp{};
     memset(&mp, 0, sizeof(mp));
     hipLaunchKernelGGL(scaled_loss_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0,
                        (hipStream_t)stream, jac, n_jac, b_total, feat, (int64_t)b * (dof > 0 ? dof : 0),
@@ -492,7 +492,7 @@ smmd_status smmd_smmd_loss_bwd_ex(const float *jac, int n_cols, int b, int b_tot
     int64_t blocks = gjac ? (n_jac / 4 + 255) / 256 : ((int64_t)(m + n) * d + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     if (blocks < 1) blocks = 1;
-    MmdBwdPart mp;
+    MmdBwdPart mp{};
     mp.g_mmd2 = g_mmd2_grad;
     mp.gxu = gx_unit;
     mp.gyu = gy_unit;

@@ -15,50 +15,38 @@
 //   U = G g G^T  (g: the 3x3 filter [k][c]; the backward-data conv uses the
 //                 flipped, transposed filter, mode 1 of the filter transform)
 //
-// Block: 64 tiles (lanes of the transform waves) x 64 output channels, 4
-// waves; wave w computes the 32 x 32 (k, tile) quadrant (kh = w >> 1, th =
-// w & 1) for all 16 points: 16 f32x16 accumulators (256 AGPRs), so for one
-// (k, tile) every point lives in the same lane and register and the output
-// transform runs in registers.  Input channels go 8 per chunk through a
-// double-buffered LDS stage (V 32 KB + U 32 KB per buffer): chunk c+1's
-// global loads are issued before chunk c's 64 MFMAs per wave; its transform
-// and LDS stores are cut into 32 slices issued one after each of the second
-// half's MFMAs (in the matrix core's shadow), one barrier per chunk.
+// Block: 64 tiles (lanes of the transform waves) x 64 output channels, 8
+// waves, two per SIMD: waves w and w + 4 share the 32 x 32 (k, tile) quadrant
+// q = w & 3 and split the 16 points (8 f32x16 accumulators each), and swap
+// accumulator halves through LDS for the output transform (wino8_body).
+// Input channels go 8 per chunk through a double-buffered LDS stage (V 32 KB +
+// U 32 KB per buffer): chunk c+1's global loads are issued before chunk c's
+// 32 MFMAs per wave; its transform and LDS stores are cut into slices issued
+// one after each MFMA (in the matrix core's shadow), one barrier per chunk.
 // Measured and not kept: a 16x16x4 form with 32 output channels per block,
 // 128 accumulator registers and two workgroups per CU (129 / 110 / 101 / 118
-// us vs 132 / 112 / 97 / 102 us on the four SNResNet-64 layers).
-#include "smmd_common.hpp"
+// us vs 132 / 112 / 97 / 102 us on the four SNResNet-64 layers); a 4-wave
+// form of this block, one wave per quadrant with all 16 points (the default
+// until r11, bit-identical, slower).
+#include "smmd_wino_common.hpp"
 #include "smmd_ldsdma.hpp"
 
 namespace smmd {
 
 namespace {
 
-constexpr int WN_T = 256;                 // threads per block
 constexpr int WN_TB = 64;                 // tiles per block
 constexpr int WN_KB = 64;                 // output channels per block
 constexpr int WN_CC = 8;                  // input channels per chunk
 constexpr int WN_STAGE = 16 * WN_CC * 64; // floats per V (and per U) stage
-// + the block's 64 biases: the epilogue reads them from LDS, so its rows never
-// wait on a global load (a load there waits, in order, for every earlier store)
+// the two V and two U stages, + the block's 64 biases (the epilogue reads them
+// from LDS, so its rows never wait on a global load: a load there waits, in
+// order, for every earlier store), + the V stages' padding of 2 floats a
+// point (W8_VP below)
 constexpr size_t WN_LDS = 2 * 2 * WN_STAGE * sizeof(float) + WN_KB * sizeof(float) +
-                          2 * 2 * 16 * sizeof(float);   // (+ the 8-wave kernel's V padding)
+                          2 * 2 * 16 * sizeof(float);
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f4v __attribute__((ext_vector_type(4)));
-typedef float f2v __attribute__((ext_vector_type(2)));
-
-// neighbour lanes' values, 0 where the source lane is outside the wave
-// (bound_ctrl: no preset of the destination)
-__device__ __forceinline__ float wn_dpp_left(float v) {    // lane l gets lane l-1's v
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x138,
-                                                              0xf, 0xf, true));
-}
-
-__device__ __forceinline__ float wn_dpp_right(float v) {   // lane l gets lane l+1's v
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x130,
-                                                              0xf, 0xf, true));
-}
+struct for_wino3x3_conv {};               // names this file's slab reduction in a profile
 
 // U = G g G^T for the filters (ko, 4 q .. 4 q + 3), stored in the conv
 // kernel's LDS order u[kb][chunk][p][h][k64][c4] (c = 4 h + c4 within the
@@ -177,8 +165,8 @@ __device__ __forceinline__ void wn_outer(const float (&tx)[4], const float (&ty)
                                          float (&tl)[4], float (&tr)[4]) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        tl[i] = wn_dpp_left(ty[i]);
-        tr[i] = wn_dpp_right(tx[i]);
+        tl[i] = dpp_from_left(ty[i]);
+        tr[i] = dpp_from_right(tx[i]);
     }
     if (EDGE) {
         if (lane == 0 && tx_ > 0) {
@@ -224,334 +212,30 @@ __device__ __forceinline__ void wn_vrow(const float (&tl)[4], const float (&tx)[
 // lands).  Its waits also retire the older filter-stage LDS-DMA (vmcnt is
 // in order): safe, at worst early.
 // (a buffer load: the base in a uniform descriptor, the lane's 32-bit byte
-// offset in one VGPR -- no 64-bit address arithmetic per load)
+// offset in one VGPR -- no 64-bit address arithmetic per load; buf_rsrc_2g)
 __device__ __forceinline__ f2v wn_ld2(uint32_t voff, __amdgpu_buffer_rsrc_t rs) {
     return __builtin_bit_cast(f2v, __builtin_amdgcn_raw_buffer_load_b64(rs, voff, 0, 0));
 }
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t wn_rsrc(const float *base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(base), 0, 0x7fffffff, 0x00020000);
-}
 
 #ifdef WN_CLOCK        // diagnostic build only (-DWN_CLOCK): per-block clock stamps
-                       // (tools/wino_pmc.py reads them through smmd_diag_wino_clock)
-__device__ unsigned long long wn_clk[4096][4];
-// the 8-wave kernel's phases, waves 0 and 4: memtime at entry, after the
+                       // (tools/wino8_phases.py reads them through smmd_diag_wino8_clock)
+// the kernel's phases, waves 0 and 4: memtime at entry, after the
 // prologue's barrier, after the chunk loop, after the epilogue's two
 // barriers, at exit; realtime at entry, exit
 __device__ unsigned long long wn_clk8[4096][2][8];
 #endif
 
-template <bool EDGE>
-__global__ __launch_bounds__(WN_T, 1) void wino_conv_kernel(
-    const float *__restrict__ x, const float *__restrict__ u, const float *__restrict__ bias,
-    float *__restrict__ y, WnGeom g) {
-    extern __shared__ float4 wn_lds[];
-    float4 *const Vs = wn_lds;                         // [2][p][h][t64]  (float4 = c4)
-    float4 *const Us = wn_lds + 2 * (WN_STAGE / 4);    // [2][p][h][k64]
-    float *const Bs = reinterpret_cast<float *>(wn_lds + 4 * (WN_STAGE / 4));   // [k64]
-
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int kb = blockIdx.y;
-    const int64_t tile0 = (int64_t)blockIdx.x * WN_TB;
-    const int nch1 = g.C / WN_CC;                       // chunks per input
-    const int nch = g.x2 ? 2 * nch1 : nch1;             // over both inputs
-#ifdef WN_CLOCK
-    const unsigned long long clk_t0 = __builtin_amdgcn_s_memtime();
-    const unsigned long long clk_r0 = __builtin_amdgcn_s_memrealtime();
-#endif
-    // input-channel slice blockIdx.z of gridDim.z: chunks [c0, c0 + nchunk)
-    const int c0 = (int)((int64_t)nch * blockIdx.z / gridDim.z);
-    const int nchunk = (int)((int64_t)nch * (blockIdx.z + 1) / gridDim.z) - c0;
-    y += (int64_t)blockIdx.z * g.slab;
-
-    // transform role: lane = tile, wave w = channels 2w, 2w+1 of each chunk
-    const int64_t gt = tile0 + lane;
-    const bool tok = gt < g.T;
-    int tn = 0, tty = 0, ttx = 0;
-    if (tok) {
-        tn = (int)(gt / g.Timg);
-        const int r = (int)(gt - (int64_t)tn * g.Timg);
-        tty = r / g.TW;
-        ttx = r - tty * g.TW;
-    }
-    const int64_t HW = (int64_t)g.H * g.W;
-
-    // The loop's global loads, all issued at the top of chunk c for chunk
-    // c + 1: its filter stage by LDS-DMA (8 asm pieces, no VGPR destination;
-    // the compiler does not count them), then its patch rows into `raw` (8
-    // ordinary loads, used in this chunk's second half: loaded and used in one
-    // iteration, so no loop-carried copy of a register still loading).  The
-    // compiler's waits for the rows also retire the older stage pieces (vmcnt
-    // is in order); a vmcnt(0) before the barrier makes that explicit.
-    // Addresses: a uniform SGPR base per chunk plus fixed per-lane byte
-    // offsets (x is under 2 GiB: smmd_wino3x3_supported).
-    f2v raw[2][4];
-    uint32_t xoff[2][4];                // byte offsets of the rows from the chunk base
-    const int TH = g.H >> 1;
-    const bool r0ok = tty > 0, r3ok = tty < TH - 1;
-#pragma unroll
-    for (int e = 0; e < 2; ++e)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int yc = min(max(2 * tty - 1 + i, 0), g.H - 1);
-            xoff[e][i] = (uint32_t)((((int64_t)tn * g.C + 2 * w + e) * HW + (int64_t)yc * g.W +
-                                     2 * ttx) * 4);
-        }
-    // chunk cc of this slice: its input and filter stage (wave-uniform)
-    auto xbase = [&](int cc) -> const float * {
-        const int c = c0 + cc;
-        return c < nch1 ? x + (int64_t)c * WN_CC * HW : g.x2 + (int64_t)(c - nch1) * WN_CC * HW;
-    };
-    auto ubase = [&](int cc) -> const float4 * {
-        const int c = c0 + cc;
-        return reinterpret_cast<const float4 *>(c < nch1 ? u : g.u2) +
-               ((int64_t)kb * nch1 + (c < nch1 ? c : c - nch1)) * (WN_STAGE / 4);
-    };
-    auto load_rows = [&](int cc) {
-        const __amdgpu_buffer_rsrc_t rs = wn_rsrc(xbase(cc));
-#pragma unroll
-        for (int e = 0; e < 2; ++e)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) raw[e][i] = wn_ld2(xoff[e][i], rs);
-    };
-    const uint32_t us_lds = lds_addr(Us) + (uint32_t)__builtin_amdgcn_readfirstlane(w) * 8192u;
-    // (per-piece lane offsets, no instruction offset: an LDS-DMA's immediate
-    // offset would move its LDS destination too)
-    uint32_t uoff[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) uoff[i] = (uint32_t)((w * 512 + i * 64 + lane) * 16);
-    auto load_u = [&](int cc) {
-        const float4 *sb = ubase(cc);
-        const uint32_t dst = us_lds + (uint32_t)(cc & 1) * (WN_STAGE * 4);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) glds16(uoff[i], sb, dst + i * 1024);
-    };
-    f32x16 acc[16];
-#pragma unroll
-    for (int p = 0; p < 16; ++p) acc[p] = f32x16{};
-
-    const int th = w & 1, kh = w >> 1, hl = lane >> 5, l32 = lane & 31;
-// 64 MFMAs per wave per chunk, the points taken in pairs so consecutive
-// MFMAs never share an accumulator; the next pair's fragments are read right
-// after each pair's first MFMA (seven MFMAs of cover for the LDS latency)
-#define WN_MFMA_CHUNK(BUF_)                                                                  \
-    do {                                                                                     \
-        const float4 *V_ = Vs + (BUF_) * (WN_STAGE / 4);                                     \
-        const float4 *U_ = Us + (BUF_) * (WN_STAGE / 4);                                     \
-        float4 a0 = U_[hl * 64 + kh * 32 + l32], b0 = V_[hl * 64 + th * 32 + l32];          \
-        float4 a1 = U_[(2 + hl) * 64 + kh * 32 + l32], b1 = V_[(2 + hl) * 64 + th * 32 + l32]; \
-        _Pragma("unroll") for (int pp = 0; pp < 8; ++pp) {                                   \
-            const int p = 2 * pp;                                                            \
-            const float4 ca0 = a0, cb0 = b0, ca1 = a1, cb1 = b1;                             \
-            _Pragma("unroll") for (int m = 0; m < 8; ++m) {                                  \
-                const int s4 = m >> 1;                                                       \
-                if ((m & 1) == 0)                                                            \
-                    acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(ca0[s4], cb0[s4], acc[p], 0, 0, 0); \
-                else                                                                         \
-                    acc[p + 1] =                                                             \
-                        __builtin_amdgcn_mfma_f32_32x32x2f32(ca1[s4], cb1[s4], acc[p + 1], 0, 0, 0); \
-                if (m == 0 && pp < 7) {                                                      \
-                    a0 = U_[((p + 2) * 2 + hl) * 64 + kh * 32 + l32];                        \
-                    b0 = V_[((p + 2) * 2 + hl) * 64 + th * 32 + l32];                        \
-                    a1 = U_[((p + 3) * 2 + hl) * 64 + kh * 32 + l32];                        \
-                    b1 = V_[((p + 3) * 2 + hl) * 64 + th * 32 + l32];                        \
-                }                                                                            \
-                __builtin_amdgcn_sched_barrier(0);                                           \
-            }                                                                                \
-        }                                                                                    \
-    } while (0)
-
-    // chunk 0 staged before the loop (everything waited for), chunk 1's rows
-    // then issued
-    const float bias_k = (bias && tid < WN_KB) ? bias[kb * WN_KB + tid] : 0.f;
-    load_u(0);
-    load_rows(0);
-    {
-        float tx[2][4], ty[2][4], tl[4], tr[4], v[2][4][4];
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            wn_own(raw[e], r0ok, r3ok, tx[e], ty[e]);
-            wn_outer<EDGE>(tx[e], ty[e], xbase(0) + ((int64_t)tn * g.C + 2 * w + e) * HW, tty, ttx,
-                           r0ok, r3ok, lane, g.TW, g.H, g.W, tl, tr);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) wn_vrow(tl, tx[e], ty[e], tr, i, v[e][i]);
-        }
-        float2 *V2 = reinterpret_cast<float2 *>(Vs);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                V2[(((i * 4 + j) * 2 + (w >> 1)) * 64 + lane) * 2 + (w & 1)] =
-                    make_float2(v[0][i][j], v[1][i][j]);
-    }
-    if (tid < WN_KB) Bs[tid] = bias_k;
-    dma_wait_all();                          // chunk 0's stage landed (the rows' waits did it)
-    __syncthreads();
-
-    for (int cc = 0; cc + 1 < nchunk; ++cc) {
-        const int buf = cc & 1, nbuf = buf ^ 1;
-        load_u(cc + 1);
-        __builtin_amdgcn_sched_barrier(0);
-        load_rows(cc + 1);
-        __builtin_amdgcn_sched_barrier(0);
-        const float4 *V_ = Vs + buf * (WN_STAGE / 4);
-        const float4 *U_ = Us + buf * (WN_STAGE / 4);
-        float4 a0 = U_[hl * 64 + kh * 32 + l32], b0 = V_[hl * 64 + th * 32 + l32];
-        float4 a1 = U_[(2 + hl) * 64 + kh * 32 + l32], b1 = V_[(2 + hl) * 64 + th * 32 + l32];
-        // first half: 32 MFMAs
-#pragma unroll
-        for (int pp = 0; pp < 4; ++pp) {
-            const int p = 2 * pp;
-            const float4 ca0 = a0, cb0 = b0, ca1 = a1, cb1 = b1;
-#pragma unroll
-            for (int m = 0; m < 8; ++m) {
-                const int s4 = m >> 1;
-                if ((m & 1) == 0)
-                    acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(ca0[s4], cb0[s4], acc[p], 0, 0, 0);
-                else
-                    acc[p + 1] =
-                        __builtin_amdgcn_mfma_f32_32x32x2f32(ca1[s4], cb1[s4], acc[p + 1], 0, 0, 0);
-                if (m == 0) {
-                    a0 = U_[((p + 2) * 2 + hl) * 64 + kh * 32 + l32];
-                    b0 = V_[((p + 2) * 2 + hl) * 64 + th * 32 + l32];
-                    a1 = U_[((p + 3) * 2 + hl) * 64 + kh * 32 + l32];
-                    b1 = V_[((p + 3) * 2 + hl) * 64 + th * 32 + l32];
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        // second half: after each MFMA one slice of chunk cc + 1's transform
-        // and V stores (the other buffer), issued in the MFMA's slot (the f32 MFMA holds the SIMD's VALU, so
-        // each slice costs its own issue time); sched_barrier pins the order
-        __builtin_amdgcn_sched_barrier(0);
-        float tx0[4], ty0[4], tx1[4], ty1[4], tl0[4], tr0[4], tl1[4], tr1[4], v0[4], v1[4];
-        const float *xc = xbase(cc + 1) + ((int64_t)tn * g.C + 2 * w) * HW;
-        float2 *Vn = reinterpret_cast<float2 *>(Vs + nbuf * (WN_STAGE / 4));
-#pragma unroll
-        for (int pp = 4; pp < 8; ++pp) {
-            const int p = 2 * pp;
-            const float4 ca0 = a0, cb0 = b0, ca1 = a1, cb1 = b1;
-#pragma unroll
-            for (int m = 0; m < 8; ++m) {
-                const int s4 = m >> 1;
-                if ((m & 1) == 0)
-                    acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(ca0[s4], cb0[s4], acc[p], 0, 0, 0);
-                else
-                    acc[p + 1] =
-                        __builtin_amdgcn_mfma_f32_32x32x2f32(ca1[s4], cb1[s4], acc[p + 1], 0, 0, 0);
-                if (m == 0 && pp < 7) {
-                    a0 = U_[((p + 2) * 2 + hl) * 64 + kh * 32 + l32];
-                    b0 = V_[((p + 2) * 2 + hl) * 64 + th * 32 + l32];
-                    a1 = U_[((p + 3) * 2 + hl) * 64 + kh * 32 + l32];
-                    b1 = V_[((p + 3) * 2 + hl) * 64 + th * 32 + l32];
-                }
-                const int K = (pp - 4) * 8 + m;
-                // (the rows are first used at slice 8: 40 MFMAs after their
-                // loads went out)
-                if (K == 8) {                        // own columns, channel 0
-                    // (an empty asm on the rows: their arithmetic cannot be
-                    // hoisted above this slot, so their wait lands here)
-                    asm volatile("" : "+v"(raw[0][0]), "+v"(raw[0][1]), "+v"(raw[0][2]),
-                                 "+v"(raw[0][3]), "+v"(raw[1][0]), "+v"(raw[1][1]),
-                                 "+v"(raw[1][2]), "+v"(raw[1][3]));
-                    wn_own(raw[0], r0ok, r3ok, tx0, ty0);
-                } else if (K == 9) {                 // own columns, channel 1
-                    wn_own(raw[1], r0ok, r3ok, tx1, ty1);
-                } else if (K == 11) {
-                    wn_outer<EDGE>(tx0, ty0, xc, tty, ttx, r0ok, r3ok, lane, g.TW, g.H, g.W,
-                                   tl0, tr0);
-                } else if (K == 13) {
-                    wn_outer<EDGE>(tx1, ty1, xc + HW, tty, ttx, r0ok, r3ok, lane, g.TW, g.H, g.W,
-                                   tl1, tr1);
-                } else if (K >= 16 && K < 20) {      // row i of V, both channels, stored
-                    const int i = K - 16;
-                    wn_vrow(tl0, tx0, ty0, tr0, i, v0);
-                    wn_vrow(tl1, tx1, ty1, tr1, i, v1);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        Vn[(((i * 4 + j) * 2 + (w >> 1)) * 64 + lane) * 2 + (w & 1)] =
-                            make_float2(v0[j], v1[j]);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        dma_wait_all();                      // chunk cc + 1's filter stage landed
-        __syncthreads();
-    }
-    WN_MFMA_CHUNK((nchunk - 1) & 1);
-
-    // epilogue: C_p[k][tile], k = (r & 3) + 8 (r >> 2) + 4 hl, tile = l32.
-    // With an even tile-row width the lane pair (2i, 2i+1) holds two
-    // neighbouring tiles: the even lane stores row 0 of both, the odd lane
-    // row 1 (one DPP swap of two floats), so every store is a float4
-    const int64_t et = tile0 + th * 32 + l32;
-    const bool eok = et < g.T;
-    const int en = eok ? (int)(et / g.Timg) : 0;
-    const int er = (int)(et - (int64_t)en * g.Timg);
-    const int ety = er / g.TW, etx = er - ety * g.TW;
-    const bool pairs = (g.TW & 1) == 0;
-    const bool odd = lane & 1;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int k = kb * WN_KB + kh * 32 + (r & 3) + 8 * (r >> 2) + 4 * hl;
-        float m[16];
-#pragma unroll
-        for (int p = 0; p < 16; ++p) m[p] = acc[p][r];
-        float s0[4], s1[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            s0[j] = m[j] + m[4 + j] + m[8 + j];
-            s1[j] = m[4 + j] - m[8 + j] - m[12 + j];
-        }
-        const float b = Bs[k - kb * WN_KB];
-        float y00 = s0[0] + s0[1] + s0[2] + b, y01 = s0[1] - s0[2] - s0[3] + b;
-        float y10 = s1[0] + s1[1] + s1[2] + b, y11 = s1[1] - s1[2] - s1[3] + b;
-        if (g.relu) {
-            y00 = fmaxf(y00, 0.f); y01 = fmaxf(y01, 0.f);
-            y10 = fmaxf(y10, 0.f); y11 = fmaxf(y11, 0.f);
-        }
-        float *o = y + (((int64_t)en * g.K + k) * g.H + 2 * ety) * g.W + 2 * etx;
-        if (pairs) {
-            // even lanes send row 1, odd lanes row 0, to the partner lane
-            const float sx = odd ? y00 : y10, sy = odd ? y01 : y11;
-            const float rx = __builtin_bit_cast(
-                float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, sx), 0xb1, 0xf, 0xf, false));
-            const float ry = __builtin_bit_cast(
-                float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, sy), 0xb1, 0xf, 0xf, false));
-            if (eok) {
-                if (!odd)
-                    *reinterpret_cast<float4 *>(o) = make_float4(y00, y01, rx, ry);
-                else
-                    *reinterpret_cast<float4 *>(o + g.W - 2) = make_float4(rx, ry, y10, y11);
-            }
-        } else if (eok) {
-            *reinterpret_cast<float2 *>(o) = make_float2(y00, y01);
-            *reinterpret_cast<float2 *>(o + g.W) = make_float2(y10, y11);
-        }
-    }
-#ifdef WN_CLOCK
-    if (tid == 0 && blockIdx.z == 0) {
-        const unsigned long long t1 = __builtin_amdgcn_s_memtime();
-        const unsigned long long r1 = __builtin_amdgcn_s_memrealtime();
-        const unsigned b = (blockIdx.y * gridDim.x + blockIdx.x) & 4095;
-        wn_clk[b][0] = clk_t0; wn_clk[b][1] = t1; wn_clk[b][2] = clk_r0; wn_clk[b][3] = r1;
-    }
-#endif
-}
-
-// The same block tile (64 tiles x 64 output channels, chunks of 8 input
-// channels, the same LDS stages) with 8 waves, two per SIMD: waves w and
-// w + 4 share a SIMD and the (k, tile) quadrant q = w & 3, and split the 16
-// points (PH = w >> 2: points 8 PH .. 8 PH + 7, 128 accumulator registers).
+// The block (64 tiles x 64 output channels, chunks of 8 input channels) on 8
+// waves, two per SIMD: waves w and w + 4 share a SIMD and the (k, tile)
+// quadrant q = w & 3, and split the 16 points (PH = w >> 2: points 8 PH ..
+// 8 PH + 7, 128 accumulator registers).
 // The f32 MFMA holds its own wave's VALU issue, but the partner wave's VALU
 // work goes out beside it (profiles/r12/mfma_valu_coissue.txt: two waves per
 // SIMD, the MFMA wave keeps its 64 cycles a slot), so the input transform --
-// one channel per wave now -- and the chunk-boundary waits of one wave are
-// covered by the other's MFMAs.  Each point's accumulation order over the
-// channels is that of wino_conv_kernel and the output transform is its
-// arithmetic term for term (the partners swap the halves of their
-// accumulators through LDS and each finishes 8 of the 16 rows), so the two
-// kernels' outputs are bit-identical.
+// one channel per wave -- and the chunk-boundary waits of one wave are
+// covered by the other's MFMAs.  Each point accumulates over the channels in
+// ascending order; for the output transform the partners swap the halves of
+// their accumulators through LDS and each finishes 8 of the 16 rows.
 constexpr int W8_T = 512;
 #ifndef W8_VPAIR
 #define W8_VPAIR 1      // the V stage in channel pairs (see store_vrow)
@@ -581,8 +265,8 @@ __device__ __forceinline__ void w8_cols(const f2v (&r)[4], f2v (&t)[4]) {
 }
 __device__ __forceinline__ void w8_row(const f2v &t, bool eL, bool eR, float (&v)[4]) {
     const float ys = eR ? 0.f : t.y, xs = eL ? 0.f : t.x;
-    v[0] = wn_dpp_left(ys) - t.y;
-    v[3] = t.x - wn_dpp_right(xs);
+    v[0] = dpp_from_left(ys) - t.y;
+    v[3] = t.x - dpp_from_right(xs);
     // (tx + ty, ty - tx) in one packed add: the low result takes (t.lo,
     // t.hi), the high one (t.hi, -t.lo)
     f2v s;
@@ -668,7 +352,7 @@ __device__ __forceinline__ void wino8_body(const float *__restrict__ x, const fl
     for (int i = 0; i < 4; ++i) {
         const int yy = 2 * tty - 1 + i;
         xoff[i] = (yy < 0 || yy >= g.H)
-                      ? 0x80000000u
+                      ? BUF_OOB
                       : (uint32_t)((((int64_t)tn * g.C + w) * HW + (int64_t)yy * g.W + 2 * ttx) * 4);
     }
     const bool eL = ttx == 0, eR = ttx == g.TW - 1;
@@ -682,7 +366,7 @@ __device__ __forceinline__ void wino8_body(const float *__restrict__ x, const fl
                ((int64_t)kb * nch1 + (c < nch1 ? c : c - nch1)) * (WN_STAGE / 4);
     };
     auto load_rows = [&](int cc) {
-        const __amdgpu_buffer_rsrc_t rs = wn_rsrc(xbase(cc));
+        const __amdgpu_buffer_rsrc_t rs = buf_rsrc_2g(xbase(cc));
 #pragma unroll
         for (int i = 0; i < 4; ++i) raw[i] = wn_ld2(xoff[i], rs);
     };
@@ -871,8 +555,8 @@ __device__ __forceinline__ void wino8_body(const float *__restrict__ x, const fl
     // tile past the end reads zeros at the out-of-range offset and is not stored)
     f2v mk[2][2][2][2];
     if constexpr (EPI == 2) {
-        const __amdgpu_buffer_rsrc_t ms = wn_rsrc(g.mask);
-        const uint32_t m0 = eok ? yo : 0x80000000u, m1 = eok ? yo1 : 0x80000000u;
+        const __amdgpu_buffer_rsrc_t ms = buf_rsrc_2g(g.mask);
+        const uint32_t m0 = eok ? yo : BUF_OOB, m1 = eok ? yo1 : BUF_OOB;
 #pragma unroll
         for (int r4 = 0; r4 < 2; ++r4)
 #pragma unroll
@@ -910,7 +594,7 @@ __device__ __forceinline__ void wino8_body(const float *__restrict__ x, const fl
     // its row-0 channel (k0) fixed, each row adding a uniform multiple of H W
     // (y under 2 GiB: smmd_wino3x3_supported); each lane stores its own
     // tile's two output rows (8 bytes each, 32 tiles of a row contiguous)
-    const __amdgpu_buffer_rsrc_t ys = wn_rsrc(y);
+    const __amdgpu_buffer_rsrc_t ys = buf_rsrc_2g(y);
     typedef unsigned u2v __attribute__((ext_vector_type(2)));
     // the output transform on row pairs (r, r + 1): both rows' values of a
     // point sit in adjacent registers (acc[p][r], acc[p][r + 1]; the
@@ -984,35 +668,6 @@ __global__ __launch_bounds__(W8_T, 1) void wino_conv8_kernel(
         wino8_body<EDGE, 0, EPI>(x, u, bias, y, g);
 }
 
-// y = bias + sum over the S partial slabs in slice order (float4 when the
-// plane size allows)
-__global__ void wino_reduce_kernel(const float *__restrict__ part, const float *__restrict__ bias,
-                                   float *__restrict__ y, int64_t n4, int S, int K, int HW,
-                                   int relu, const float *__restrict__ mask) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n4) return;
-    const float4 *p4 = reinterpret_cast<const float4 *>(part);
-    float4 s = p4[i];
-    for (int z = 1; z < S; ++z) {
-        const float4 t = p4[i + z * n4];
-        s.x += t.x; s.y += t.y; s.z += t.z; s.w += t.w;
-    }
-    if (bias) {
-        const float b = bias[(int)((i * 4 / HW) % K)];
-        s.x += b; s.y += b; s.z += b; s.w += b;
-    }
-    if (relu == 1) {
-        s.x = fmaxf(s.x, 0.f); s.y = fmaxf(s.y, 0.f); s.z = fmaxf(s.z, 0.f); s.w = fmaxf(s.w, 0.f);
-    } else if (relu == 2) {
-        const float4 m = reinterpret_cast<const float4 *>(mask)[i];
-        s.x = m.x <= 0.f ? 0.f : s.x;
-        s.y = m.y <= 0.f ? 0.f : s.y;
-        s.z = m.z <= 0.f ? 0.f : s.z;
-        s.w = m.w <= 0.f ? 0.f : s.w;
-    }
-    reinterpret_cast<float4 *>(y)[i] = s;
-}
-
 }  // namespace
 
 // input-channel slices for a grid of `blocks` workgroups: enough for one
@@ -1025,21 +680,11 @@ static int wino_slices(int64_t blocks, int nch, int HW) {
     return S;
 }
 
-// SMMD_WINO8=0: the 4-wave form (A/B and tests; the two are bit-identical)
-static bool wino8_enabled() {
-    const char *e = getenv("SMMD_WINO8");
-    return !(e && e[0] == '0');
-}
-
 }  // namespace smmd
 
 using namespace smmd;
 
 #ifdef WN_CLOCK
-extern "C" int smmd_diag_wino_clock(unsigned long long *host, int n) {
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(wn_clk), sizeof(unsigned long long) * 4 * n) ==
-                   hipSuccess ? 0 : 1;
-}
 extern "C" int smmd_diag_wino8_clock(unsigned long long *host, int n) {
     return hipMemcpyFromSymbol(host, HIP_SYMBOL(wn_clk8), sizeof(unsigned long long) * 16 * n) ==
                    hipSuccess ? 0 : 1;
@@ -1106,10 +751,10 @@ static smmd_status wino3x3_conv(const float *x, const float *u, const float *x2,
          reinterpret_cast<uintptr_t>(u) | reinterpret_cast<uintptr_t>(x2) |
          reinterpret_cast<uintptr_t>(u2) | reinterpret_cast<uintptr_t>(mask)) & 15)
         return SMMD_EINVAL;
-    // the mask epilogue is the 8-wave kernel's (the 4-wave form: unsupported)
-    if (relu == 2 && !wino8_enabled()) return SMMD_EUNSUPPORTED;
     const int pair = x2 ? 2 : 1;
-    WnGeom g;
+    // (zero-filled before its fields are set, like every launch argument
+    // struct: a field added later must read as "off", never as stack garbage)
+    WnGeom g{};
     g.mask = mask;
     g.x2 = x2;
     g.u2 = u2;
@@ -1129,9 +774,7 @@ static smmd_status wino3x3_conv(const float *x, const float *u, const float *x2,
     }
     static bool attr = false;
     if (!attr) {
-        const void *ks[8] = {reinterpret_cast<const void *>(wino_conv_kernel<false>),
-                             reinterpret_cast<const void *>(wino_conv_kernel<true>),
-                             reinterpret_cast<const void *>(wino_conv8_kernel<false, 0>),
+        const void *ks[6] = {reinterpret_cast<const void *>(wino_conv8_kernel<false, 0>),
                              reinterpret_cast<const void *>(wino_conv8_kernel<true, 0>),
                              reinterpret_cast<const void *>(wino_conv8_kernel<false, 1>),
                              reinterpret_cast<const void *>(wino_conv8_kernel<true, 1>),
@@ -1146,34 +789,25 @@ static smmd_status wino3x3_conv(const float *x, const float *u, const float *x2,
     g.slab = S > 1 ? total : 0;
     g.relu = S > 1 ? 0 : relu;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)tb, (unsigned)(ko / WN_KB), (unsigned)S);
     const float *b1 = S > 1 ? nullptr : bias;
     // tile rows that are whole lane groups of a wave need no edge loads
     const bool edge = 64 % g.TW != 0;
-    if (wino8_enabled()) {
-        g.TB = (int)tb;
-        g.KB = ko / WN_KB;
-        g.S = S;
-        const int64_t nblk = tb * g.KB * S;
-        if (nblk > 0x7fffffff) return SMMD_EINVAL;
-        auto k8 = edge ? (g.relu == 2   ? wino_conv8_kernel<true, 2>
-                          : g.relu ? wino_conv8_kernel<true, 1>
-                                   : wino_conv8_kernel<true, 0>)
-                       : (g.relu == 2   ? wino_conv8_kernel<false, 2>
-                          : g.relu ? wino_conv8_kernel<false, 1>
-                                   : wino_conv8_kernel<false, 0>);
-        k8<<<dim3((unsigned)nblk), dim3(W8_T), WN_LDS, st>>>(x, u, b1, out, g);
-    } else if (!edge) {
-        wino_conv_kernel<false><<<grid, dim3(WN_T), WN_LDS, st>>>(x, u, b1, out, g);
-    } else {
-        wino_conv_kernel<true><<<grid, dim3(WN_T), WN_LDS, st>>>(x, u, b1, out, g);
-    }
+    g.TB = (int)tb;
+    g.KB = ko / WN_KB;
+    g.S = S;
+    const int64_t nblk = tb * g.KB * S;
+    if (nblk > 0x7fffffff) return SMMD_EINVAL;
+    auto k8 = edge ? (g.relu == 2   ? wino_conv8_kernel<true, 2>
+                      : g.relu ? wino_conv8_kernel<true, 1>
+                               : wino_conv8_kernel<true, 0>)
+                   : (g.relu == 2   ? wino_conv8_kernel<false, 2>
+                      : g.relu ? wino_conv8_kernel<false, 1>
+                               : wino_conv8_kernel<false, 0>);
+    k8<<<dim3((unsigned)nblk), dim3(W8_T), WN_LDS, st>>>(x, u, b1, out, g);
     smmd_status e = last_launch_status();
     if (e != SMMD_OK || S == 1) return e;
-    const int64_t n4 = total / 4;
-    wino_reduce_kernel<<<dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st>>>(
-        out, bias, y, n4, S, ko, h * w_img, relu, mask);
-    return last_launch_status();
+    return slab_reduce_bias<for_wino3x3_conv>(out, bias, y, total / 4, S, ko, h * w_img, relu == 1,
+                                              mask, 0, st);
 }
 
 extern "C" smmd_status smmd_wino3x3_conv(const float *x, const float *u, const float *bias,

@@ -18,7 +18,7 @@
 // quadrant for all 9 points (9 f32x16 accumulators); chunks of 8 phase
 // channels (2 input channels x 4 phases) through a double-buffered 36 KB LDS
 // stage, so two workgroups fit a CU.
-#include "smmd_common.hpp"
+#include "smmd_wino_common.hpp"
 #include "smmd_ldsdma.hpp"
 
 namespace smmd {
@@ -34,30 +34,9 @@ constexpr int S2_STAGE = 9 * 8 * 64;         // floats per V (and per U) stage
 // there would wait, in order, for every earlier store)
 constexpr size_t S2_LDS = 2 * 2 * S2_STAGE * sizeof(float) + S2_KB * sizeof(float);
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f4v __attribute__((ext_vector_type(4)));
-
-// neighbour lanes' values, 0 where the source lane is outside the wave
-// (bound_ctrl: no preset of the destination; every VALU instruction costs
-// SIMD time beside the f32 MFMA, profiles/r12/mfma_valu_coissue.txt)
-__device__ __forceinline__ float s2_from_left(float v) {    // lane l gets lane l-1's v
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x138,
-                                                              0xf, 0xf, true));
-}
-
-__device__ __forceinline__ float s2_from_right(float v) {   // lane l gets lane l+1's v
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x130,
-                                                              0xf, 0xf, true));
-}
-
-// buffer access: a wave-uniform base in the descriptor, the lane's 32-bit
-// byte offset in one VGPR (no 64-bit address arithmetic per access; tensors
-// under 2 GiB, the *_supported checks: the range is 0x7fffffff bytes and
-// S2_OOB = 2^31 its out-of-range sentinel); an offset past the range reads zeros
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t s2_rsrc(const void *base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, 0x7fffffff, 0x00020000);
-}
-constexpr uint32_t S2_OOB = 0x80000000u;
+// name this file's slab reductions in a profile
+struct for_wino4x4s2_conv {};
+struct for_wino4x4s2t_conv {};
 
 // The 16 taps of filter q of W': with sig NULL read from w [q][16]; else w is
 // the raw weight of a spectrally normalised layer and the taps are those of
@@ -223,7 +202,7 @@ __global__ __launch_bounds__(S2_T, 2) void s2_conv_kernel(
     for (int a = 0; a < 3; ++a) {
         const int yy = 4 * tty - 1 + pi + 2 * a;
         xo[a] = (yy < 0 || yy >= g.H)
-                    ? S2_OOB
+                    ? BUF_OOB
                     : (uint32_t)((((int64_t)tn * g.C + e) * HW + (int64_t)yy * g.W + 4 * ttx) * 4);
     }
     const int64_t x2shift = g.x2 ? (int64_t)(reinterpret_cast<uintptr_t>(g.x2) -
@@ -246,7 +225,7 @@ __global__ __launch_bounds__(S2_T, 2) void s2_conv_kernel(
     f4v raw[3];
     auto load_rows = [&](int cc) {
         const __amdgpu_buffer_rsrc_t rs =
-            s2_rsrc(reinterpret_cast<const char *>(x) + xshift(cc));
+            buf_rsrc_2g(reinterpret_cast<const char *>(x) + xshift(cc));
 #pragma unroll
         for (int a = 0; a < 3; ++a)
             raw[a] = __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(rs, xo[a], 0, 0));
@@ -286,7 +265,7 @@ __global__ __launch_bounds__(S2_T, 2) void s2_conv_kernel(
                 const int yy = 4 * tty - 1 + pi + 2 * a;
                 const bool row = yy >= 0 && yy < g.H;     // (outside: loaded as zeros)
                 const float c0v = raw[a].x, c1v = raw[a].y, c2v = raw[a].z, c3v = raw[a].w;
-                float L = s2_from_left(c3v), R = s2_from_right(c0v);
+                float L = dpp_from_left(c3v), R = dpp_from_right(c0v);
                 if (ttx > 0 && lane == 0) L = row ? xc[(int64_t)yy * g.W + 4 * ttx - 1] : 0.f;
                 if (ttx < g.TW - 1 && lane == 63) R = row ? xc[(int64_t)yy * g.W + 4 * ttx + 4] : 0.f;
                 L = ttx == 0 ? 0.f : L;
@@ -309,12 +288,12 @@ __global__ __launch_bounds__(S2_T, 2) void s2_conv_kernel(
         float v0[3], v1[3];
         if constexpr (!EDGE) {
             const float ws = eR ? 0.f : t[i].w, xs = eL ? 0.f : t[i].x;
-            v0[0] = s2_from_left(ws) - t[i].y;      // columns (L, 1, 3)
+            v0[0] = dpp_from_left(ws) - t[i].y;      // columns (L, 1, 3)
             v0[1] = t[i].y;
             v0[2] = t[i].w - t[i].y;
             v1[0] = t[i].x - t[i].z;                // columns (0, 2, R)
             v1[1] = t[i].z;
-            v1[2] = s2_from_right(xs) - t[i].z;
+            v1[2] = dpp_from_right(xs) - t[i].z;
         } else {
             v0[0] = d0[i][0] - d0[i][1];
             v0[1] = d0[i][1];
@@ -394,14 +373,13 @@ __global__ __launch_bounds__(S2_T, 2) void s2_conv_kernel(
     const int er = (int)(et - (int64_t)en * g.Timg);
     const int ety = er / g.TW, etx = er - ety * g.TW;
     const int Ho = g.H / 2, Wo = g.W / 2;
-    typedef float f2v __attribute__((ext_vector_type(2)));
     typedef unsigned u2v __attribute__((ext_vector_type(2)));
     const int kl0 = kh * 32 + 4 * hl;                       // k - 64 kb of row 0
     const uint32_t o0 = (uint32_t)(((((int64_t)en * g.K + kb * S2_KB + kl0) * Ho + 2 * ety) * Wo +
                                      2 * etx) * 4);
     const uint32_t o1 = o0 + (uint32_t)Wo * 4;
     const uint32_t hw4 = (uint32_t)Ho * (uint32_t)Wo * 4;
-    const __amdgpu_buffer_rsrc_t ys = s2_rsrc(y);
+    const __amdgpu_buffer_rsrc_t ys = buf_rsrc_2g(y);
     // ACC: the earlier values, all loaded before the first store (a load
     // after a store to the same buffer would wait for it: one latency per row
     // pair instead of one per block)
@@ -567,7 +545,6 @@ __device__ __forceinline__ void s2t_body(const float *__restrict__ gy, const flo
 
     // the rows by buffer loads: chunk cc's base (k = 8 (c0 + cc)) uniform, the
     // lane's offsets fixed; a row outside the image reads zeros
-    typedef float f2v __attribute__((ext_vector_type(2)));
     f2v raw[2][3];
     uint32_t roff[2][3];
 #pragma unroll
@@ -576,12 +553,12 @@ __device__ __forceinline__ void s2t_body(const float *__restrict__ gy, const flo
         for (int a = 0; a < 3; ++a) {
             const int yy = 2 * tty - 1 + qi + a;
             roff[e][a] = (yy < 0 || yy >= g.Hg)
-                             ? S2_OOB
+                             ? BUF_OOB
                              : (uint32_t)((((int64_t)tn * g.K + 2 * w + e) * HW +
                                            (int64_t)yy * g.Wg + 2 * ttx) * 4);
         }
     auto load_rows = [&](int cc) {
-        const __amdgpu_buffer_rsrc_t rs = s2_rsrc(gy + ((int64_t)c0 + cc) * 8 * HW);
+        const __amdgpu_buffer_rsrc_t rs = buf_rsrc_2g(gy + ((int64_t)c0 + cc) * 8 * HW);
 #pragma unroll
         for (int e = 0; e < 2; ++e)
 #pragma unroll
@@ -633,7 +610,7 @@ __device__ __forceinline__ void s2t_body(const float *__restrict__ gy, const flo
                     const bool row = (a == 0 && qi == 0) ? tty > 0
                                      : (a == 2 && qi == 1) ? tty < THg - 1 : true;
                     const float cx = raw[e][a].x, cy = raw[e][a].y;
-                    float L = s2_from_left(cy), R = s2_from_right(cx);
+                    float L = dpp_from_left(cy), R = dpp_from_right(cx);
                     if (ttx > 0 && lane == 0) L = row ? gc[(int64_t)yy * g.Wg + 2 * ttx - 1] : 0.f;
                     if (ttx < g.TW - 1 && lane == 63)
                         R = row ? gc[(int64_t)yy * g.Wg + 2 * ttx + 2] : 0.f;
@@ -661,14 +638,14 @@ __device__ __forceinline__ void s2t_body(const float *__restrict__ gy, const flo
             if constexpr (!EDGE) {
                 if (qj == 0) {          // columns (L, x, y)
                     const float ys = eR ? 0.f : t[e][i].y;
-                    v[e][0] = s2_from_left(ys) - t[e][i].x;
+                    v[e][0] = dpp_from_left(ys) - t[e][i].x;
                     v[e][1] = t[e][i].x;
                     v[e][2] = t[e][i].y - t[e][i].x;
                 } else {                // columns (x, y, R)
                     const float xs = eL ? 0.f : t[e][i].x;
                     v[e][0] = t[e][i].x - t[e][i].y;
                     v[e][1] = t[e][i].y;
-                    v[e][2] = s2_from_right(xs) - t[e][i].y;
+                    v[e][2] = dpp_from_right(xs) - t[e][i].y;
                 }
             } else {
                 v[e][0] = dd[e][i][0] - dd[e][i][1];
@@ -748,14 +725,14 @@ __device__ __forceinline__ void s2t_body(const float *__restrict__ gy, const flo
                                      4 * etx + qj) * 4);
     const uint32_t o1 = o0 + (uint32_t)Wx * 8;            // output row + 2
     const uint32_t hw4 = (uint32_t)Hx * (uint32_t)Wx * 4;
-    const __amdgpu_buffer_rsrc_t ds = s2_rsrc(dx);
+    const __amdgpu_buffer_rsrc_t ds = buf_rsrc_2g(dx);
     // the mask's 64 values of the lane, all loaded before the first store (the
     // stage's registers are free here): one latency per block instead of one
     // per output row pair
     float mk[16][4];
     const bool masked = g.mask != nullptr;
     if (masked) {
-        const __amdgpu_buffer_rsrc_t ms = s2_rsrc(g.mask);
+        const __amdgpu_buffer_rsrc_t ms = buf_rsrc_2g(g.mask);
 #pragma unroll
         for (int r = 0; r < 16; r += 2) {
 #pragma unroll
@@ -819,36 +796,6 @@ __global__ __launch_bounds__(S2_T, 2) void s2t_conv_kernel(
     case 2: s2t_body<EDGE, 1, 0>(gy, u, bias, dx, g, tb, cb, sl); break;
     default: s2t_body<EDGE, 1, 1>(gy, u, bias, dx, g, tb, cb, sl); break;
     }
-}
-
-// (mask: the transposed conv's ReLU mask, applied after the bias)
-__global__ void s2_reduce_kernel(const float *__restrict__ part, const float *__restrict__ bias,
-                                 float *__restrict__ y, int64_t n4, int S, int K, int HW,
-                                 const float *__restrict__ mask, int acc) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n4) return;
-    const float4 *p4 = reinterpret_cast<const float4 *>(part);
-    const float4 mv = mask ? reinterpret_cast<const float4 *>(mask)[i] : float4{};
-    float4 s = p4[i];
-    for (int z = 1; z < S; ++z) {
-        const float4 t = p4[i + z * n4];
-        s.x += t.x; s.y += t.y; s.z += t.z; s.w += t.w;
-    }
-    if (bias) {
-        const float b = bias[(int)((i * 4 / HW) % K)];
-        s.x += b; s.y += b; s.z += b; s.w += b;
-    }
-    if (mask) {
-        s.x = mv.x <= 0.f ? 0.f : s.x;
-        s.y = mv.y <= 0.f ? 0.f : s.y;
-        s.z = mv.z <= 0.f ? 0.f : s.z;
-        s.w = mv.w <= 0.f ? 0.f : s.w;
-    }
-    if (acc) {                  // y += the result
-        const float4 o = reinterpret_cast<const float4 *>(y)[i];
-        s = make_float4(o.x + s.x, o.y + s.y, o.z + s.z, o.w + s.w);
-    }
-    reinterpret_cast<float4 *>(y)[i] = s;
 }
 
 }  // namespace
@@ -933,7 +880,7 @@ static smmd_status s2_conv(const float *x, const float *u, const float *x2, cons
          reinterpret_cast<uintptr_t>(u2)) & 15)
         return SMMD_EINVAL;
     const int pair = x2 ? 2 : 1;
-    S2Geom g;
+    S2Geom g{};
     g.x2 = x2;
     g.u2 = u2;
     g.N = n; g.C = ci; g.K = ko; g.H = h; g.W = w_img;
@@ -973,11 +920,8 @@ static smmd_status s2_conv(const float *x, const float *u, const float *x2, cons
     k<<<grid, dim3(S2_T), S2_LDS, st>>>(x, u, b1, out, g);
     smmd_status e = last_launch_status();
     if (e != SMMD_OK || S == 1) return e;
-    const int64_t n4 = total / 4;
-    s2_reduce_kernel<<<dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st>>>(out, bias, y, n4,
-                                                                              S, ko, HWo, nullptr,
-                                                                              acc);
-    return last_launch_status();
+    return slab_reduce_bias<for_wino4x4s2_conv>(out, bias, y, total / 4, S, ko, HWo, 0, nullptr,
+                                                acc, st);
 }
 
 extern "C" smmd_status smmd_wino4x4s2_conv(const float *x, const float *u, const float *bias,
@@ -1063,7 +1007,7 @@ static smmd_status s2t_launch(const float *gy, const float *u, const float *bias
     if ((reinterpret_cast<uintptr_t>(gy) | reinterpret_cast<uintptr_t>(dx) |
          reinterpret_cast<uintptr_t>(u) | reinterpret_cast<uintptr_t>(mask)) & 15)
         return SMMD_EINVAL;
-    S2TGeom g;
+    S2TGeom g{};
     g.N = n; g.K = k; g.C = c; g.Hg = hg; g.Wg = wg;
     g.TW = wg / 2;
     g.Timg = (hg / 2) * g.TW;
@@ -1105,10 +1049,9 @@ static smmd_status s2t_launch(const float *gy, const float *u, const float *bias
         s2t_conv_kernel<true><<<grid, dim3(S2_T), S2_LDS, st>>>(gy, u, b1, out, g);
     smmd_status e = last_launch_status();
     if (e != SMMD_OK || S == 1) return e;
-    const int64_t n4 = total / 4;
-    s2_reduce_kernel<<<dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st>>>(
-        out, bias, dx, n4, S, c, 4 * hg * wg, mask, 0);
-    return last_launch_status();
+    // (mask: the ReLU mask, applied after the bias)
+    return slab_reduce_bias<for_wino4x4s2t_conv>(out, bias, dx, total / 4, S, c, 4 * hg * wg, 0,
+                                                 mask, 0, st);
 }
 
 extern "C" smmd_status smmd_wino4x4s2t_conv(const float *gy, const float *u, const float *bias,

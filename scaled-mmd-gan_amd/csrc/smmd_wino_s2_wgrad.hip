@@ -27,14 +27,14 @@
 // between the previous k-step's MFMAs.  Epilogue: the tp = 1 waves hand their
 // accumulators to the tp = 0 waves through LDS, which apply G^T . G and write
 // the slice's partial dW' [K][C][16]; the slices are added in order.
-#include "smmd_common.hpp"
+#include "smmd_wino_common.hpp"
 
 namespace smmd {
 
 namespace {
 
 constexpr int W2_T = 512;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+struct for_wino4x4s2_wgrad {};          // names this file's slab reductions in a profile
 
 // chunk geometry: CT tile columns (= the whole tile row), RT tile rows per
 // image, NI images; CT * RT * NI = 16 tiles
@@ -85,7 +85,6 @@ __global__ __launch_bounds__(W2_T, 1) void s2_wgrad_kernel(
 
     // buffer loads: rows outside the image read as zeros (offset past the range)
     float4 xr[P::NX], gr[P::NG];
-    constexpr uint32_t OOB = 0x80000000u;
     auto gload = [&](int64_t chunk) {
         int n0, ty0;
         if (P::NI > 1) {
@@ -111,7 +110,7 @@ __global__ __launch_bounds__(W2_T, 1) void s2_wgrad_kernel(
             const int yy = 4 * ty0 - 1 + r;
             const uint32_t off = (yy >= 0 && yy < g.H)
                                      ? (uint32_t)((img * g.C + c) * HW + yy * g.W + 4 * f) * 4u
-                                     : OOB;
+                                     : BUF_OOB;
             xr[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xs, off, 0, 0));
         }
 #pragma unroll
@@ -290,43 +289,6 @@ __global__ __launch_bounds__(W2_T, 1) void s2_wgrad_kernel(
     }
 }
 
-// out[i] = sum of the S slabs of n4 float4 each, in slab order
-// (acc: out += the sum, a weight's later gradient contribution)
-__global__ void s2w_sum_kernel(const float4 *__restrict__ part, int S, int64_t n4,
-                               float4 *__restrict__ out, int acc) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n4) return;
-    float4 a = part[i];
-    for (int s = 1; s < S; ++s) {
-        const float4 v = part[(int64_t)s * n4 + i];
-        a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-    }
-    if (acc) {
-        const float4 o = out[i];
-        a = make_float4(o.x + a.x, o.y + a.y, o.z + a.z, o.w + a.w);
-    }
-    out[i] = a;
-}
-
-// the first level for many slices: out[g] = slices g G .. g G + G - 1, in order
-__global__ void s2w_group_kernel(const float4 *__restrict__ part, int S, int G, int64_t nf4,
-                                 int ngroups, float4 *__restrict__ out) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= nf4 * ngroups) return;
-    const int gi = (int)(idx / nf4);
-    const int64_t f = idx - (int64_t)gi * nf4;
-    const int s0 = gi * G, s1 = min(S, s0 + G);
-    float4 a = part[(int64_t)s0 * nf4 + f];
-    for (int s = s0 + 1; s < s1; ++s) {
-        const float4 v = part[(int64_t)s * nf4 + f];
-        a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-    }
-    out[idx] = a;
-}
-
-constexpr int S2W_GROUP = 16;
-int s2w_groups(int S) { return S > 2 * S2W_GROUP ? (S + S2W_GROUP - 1) / S2W_GROUP : 0; }
-
 // (CT, RT) of the chunk for output tile grid TH x TW (0: not tiled)
 int s2w_shape(int TH, int TW, int *rt) {
     if (TW == 16) { *rt = 1; return 16; }
@@ -334,12 +296,6 @@ int s2w_shape(int TH, int TW, int *rt) {
     if (TW == 4 && TH % 4 == 0) { *rt = 4; return 4; }
     if (TW == 2 && TH == 2) { *rt = 2; return 2; }
     return 0;
-}
-
-int s2w_slices(int blocks, int64_t nchunks) {
-    int64_t S = (256 + blocks - 1) / blocks;
-    S = min(S, max((int64_t)1, nchunks / 4));      // at least 4 chunks (64 tiles) per slice
-    return (int)max((int64_t)1, S);
 }
 
 template <int CT, int RT>
@@ -376,8 +332,8 @@ extern "C" int smmd_wino4x4s2_wgrad_supported(int n, int ci, int co, int h, int 
 extern "C" size_t smmd_wino4x4s2_wgrad_workspace_bytes(int n, int ci, int co, int h, int w_img) {
     if (!smmd_wino4x4s2_wgrad_supported(n, ci, co, h, w_img)) return 0;
     const int64_t T = (int64_t)n * (h / 4) * (w_img / 4);
-    const int S = s2w_slices((co / 64) * (ci / 16), T / 16);
-    return (size_t)(S + s2w_groups(S)) * co * ci * 16 * sizeof(float);
+    const int S = slab_slices((co / 64) * (ci / 16), T / 16, 4);   // 4 chunks: 64 tiles
+    return (size_t)(S + slab_groups(S)) * co * ci * 16 * sizeof(float);
 }
 
 // gw [co, ci, 4, 4] = the weight gradient of conv(x [n, ci, h, w], W', stride 2,
@@ -398,7 +354,7 @@ static smmd_status s2w_launch_all(const float *x, const float *gy, float *gw, in
     if (!ws || ws_bytes < smmd_wino4x4s2_wgrad_workspace_bytes(n, ci, co, h, w_img))
         return SMMD_EWORKSPACE;
     if (reinterpret_cast<uintptr_t>(ws) & 15) return SMMD_EINVAL;
-    S2wGeom g;
+    S2wGeom g{};
     g.N = n; g.C = ci; g.K = co; g.H = h; g.W = w_img;
     g.TH = h / 4; g.TW = w_img / 4;
     g.Timg = g.TH * g.TW;
@@ -407,7 +363,7 @@ static smmd_status s2w_launch_all(const float *x, const float *gy, float *gw, in
     const int ct = s2w_shape(g.TH, g.TW, &rt);
     const int blocks = (co / 64) * (ci / 16);
     const int64_t nchunks = g.T / 16;
-    const int S = s2w_slices(blocks, nchunks);
+    const int S = slab_slices(blocks, nchunks, 4);
     g.chunks_per_slice = (int)((nchunks + S - 1) / S);
     const int Sused = (int)((nchunks + g.chunks_per_slice - 1) / g.chunks_per_slice);
     float *part = static_cast<float *>(ws);
@@ -416,23 +372,7 @@ static smmd_status s2w_launch_all(const float *x, const float *gy, float *gw, in
                     : ct == 4 ? s2w_launch<4, 4>(x, gy, part, g, Sused, st)
                               : s2w_launch<2, 2>(x, gy, part, g, Sused, st);
     if (e != SMMD_OK) return e;
-    const int64_t nf4 = (int64_t)co * ci * 4;
-    const int ng = s2w_groups(Sused);
-    int Sfin = Sused;
-    if (ng > 0) {
-        float *grp = part + (size_t)S * co * ci * 16;
-        const int64_t nt = nf4 * ng;
-        s2w_group_kernel<<<dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st>>>(
-            reinterpret_cast<const float4 *>(part), Sused, S2W_GROUP, nf4, ng,
-            reinterpret_cast<float4 *>(grp));
-        e = last_launch_status();
-        if (e != SMMD_OK) return e;
-        part = grp;
-        Sfin = ng;
-    }
-    s2w_sum_kernel<<<dim3((unsigned)((nf4 + 255) / 256)), dim3(256), 0, st>>>(
-        reinterpret_cast<const float4 *>(part), Sfin, nf4, reinterpret_cast<float4 *>(gw), acc);
-    return last_launch_status();
+    return slab_sum<for_wino4x4s2_wgrad>(part, Sused, S, (int64_t)co * ci * 4, gw, acc, st);
 }
 
 extern "C" smmd_status smmd_wino4x4s2_wgrad(const float *x, const float *gy, float *gw, int n,

@@ -17,7 +17,7 @@
 // neighbours: TW is even).  Each slice writes its partial dU [K][C][16] to the
 // workspace; smmd_wino3x3_wgrad adds the slices in order (in groups of 16 first
 // when there are more than 32) and applies G^T . G.
-#include "smmd_common.hpp"
+#include "smmd_wino_common.hpp"
 
 namespace smmd {
 
@@ -28,8 +28,7 @@ constexpr int WG_TC = 8;                       // tiles per chunk
 constexpr int WG_STAGE = 16 * WG_TC * 64;      // floats per dM (and per V) stage
 constexpr size_t WG_LDS = 2 * 2 * WG_STAGE * sizeof(float);   // 128 KB
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f2v __attribute__((ext_vector_type(2)));
+struct for_wino3x3_wgrad {};                   // names this file's slab reductions in a profile
 
 // one v_pk_add_f32 each (VOP3P: op_sel / op_sel_hi pick each source's half for
 // the low / high result, neg_lo / neg_hi negate it; written as vector ops the
@@ -214,24 +213,6 @@ __global__ __launch_bounds__(WG_T, 1) void wino_wgrad_kernel(
     }
 }
 
-// the first level of the slice reduction: out[g] = sum of slices g*G .. g*G+G-1
-// in order, one thread per (group, float4 of dU): the many-slice layers (the
-// 64-channel layer has 512) read their partials at the full width of the chip
-__global__ void wino_wgrad_group_kernel(const float4 *__restrict__ part, int S, int G,
-                                        int64_t nf4, int ngroups, float4 *__restrict__ out) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= nf4 * ngroups) return;
-    const int gi = (int)(idx / nf4);
-    const int64_t f = idx - (int64_t)gi * nf4;
-    const int s0 = gi * G, s1 = min(S, s0 + G);
-    float4 a = part[(int64_t)s0 * nf4 + f];
-    for (int s = s0 + 1; s < s1; ++s) {
-        const float4 v = part[(int64_t)s * nf4 + f];
-        a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-    }
-    out[idx] = a;
-}
-
 // dW[k][c] = G^T (sum over slices, in order, of dU) G, G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]]
 __global__ void wino_wgrad_final_kernel(const float *__restrict__ part, int S, int K, int C,
                                         float *__restrict__ dw, int acc) {
@@ -357,7 +338,6 @@ __device__ __forceinline__ void wgrad2_body(const float *__restrict__ x,
     // (same value, same LDS slot): no branch.
     float4 xr[P::NX], gr[P::NG];
     float hr[P::NH > 0 ? P::NH : 1];
-    constexpr uint32_t OOB = 0x80000000u;
     const uint32_t plane = (uint32_t)HW * 4u;
     auto gload = [&](int64_t chunk64) {
         // 32-bit (the chunk count is far below 2^31): the 64-bit division
@@ -378,7 +358,7 @@ __device__ __forceinline__ void wgrad2_body(const float *__restrict__ x,
             const int yy = 2 * ty0 - 1 + r;
             const uint32_t off = (yy >= 0 && yy < g.H)
                                      ? c * plane + (uint32_t)(yy * g.W + 2 * tx0 + 4 * f) * 4u
-                                     : OOB;
+                                     : BUF_OOB;
             xr[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xs, off, 0, 0));
         }
 #pragma unroll
@@ -398,7 +378,7 @@ __device__ __forceinline__ void wgrad2_body(const float *__restrict__ x,
                 const int yy = 2 * ty0 - 1 + r;
                 const int col = side ? 2 * tx0 + 2 * CT : 2 * tx0 - 1;
                 const bool in = yy >= 0 && yy < g.H && (side ? tx0 + CT < g.TW : tx0 > 0);
-                const uint32_t off = in ? c * plane + (uint32_t)(yy * g.W + col) * 4u : OOB;
+                const uint32_t off = in ? c * plane + (uint32_t)(yy * g.W + col) * 4u : BUF_OOB;
                 hr[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xs, off, 0, 0));
             }
         }
@@ -619,37 +599,7 @@ __global__ __launch_bounds__(WG2_T, 1) void wino_wgrad2_kernel(
         wgrad2_body<CT, 0>(x, gy, part, g);
 }
 
-// out[i] = sum of the S slabs of n4 float4 each, in slab order (the last
-// level of the r11 slice reduction, straight into dW)
-// (acc: out += the sum, the later contribution of a weight used twice: the
-// same add autograd would run, convops._late_gw)
-__global__ void wino_wgrad_sum_kernel(const float4 *__restrict__ part, int S, int64_t n4,
-                                      float4 *__restrict__ out, int acc) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n4) return;
-    float4 a = part[i];
-    for (int s = 1; s < S; ++s) {
-        const float4 v = part[(int64_t)s * n4 + i];
-        a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-    }
-    if (acc) {
-        const float4 o = out[i];
-        a = make_float4(o.x + a.x, o.y + a.y, o.z + a.z, o.w + a.w);
-    }
-    out[i] = a;
-}
-
 }  // namespace
-
-static int wgrad_slices(int blocks, int64_t nchunks) {
-    int64_t S = (256 + blocks - 1) / blocks;
-    S = min(S, max((int64_t)1, nchunks / 8));      // at least 8 chunks per slice
-    return (int)max((int64_t)1, S);
-}
-
-constexpr int WG_GROUP = 16;                       // slices per first-level group
-
-static int wgrad_groups(int S) { return S > 2 * WG_GROUP ? (S + WG_GROUP - 1) / WG_GROUP : 0; }
 
 // the r11 kernel's chunk shape for a tile-row width (0: not tiled by it)
 static int wgrad2_ct(int h, int w_img) {
@@ -667,12 +617,6 @@ static bool wgrad_v1_forced() {
     return e && e[0] == '1';
 }
 
-static int wgrad2_slices(int blocks, int64_t nchunks) {
-    int64_t S = (256 + blocks - 1) / blocks;
-    S = min(S, max((int64_t)1, nchunks / 4));      // at least 4 chunks (64 tiles) per slice
-    return (int)max((int64_t)1, S);
-}
-
 }  // namespace smmd
 
 using namespace smmd;
@@ -685,14 +629,14 @@ extern "C" int smmd_wino3x3_wgrad_supported(int n, int ci, int co, int h, int w_
 
 static size_t wgrad_v1_ws(int n, int ci, int co, int h, int w_img) {
     const int64_t T = (int64_t)n * (h / 2) * (w_img / 2);
-    const int S = wgrad_slices((co / 64) * (ci / 64), (T + WG_TC - 1) / WG_TC);
-    return (size_t)(S + wgrad_groups(S)) * co * ci * 16 * sizeof(float);
+    const int S = slab_slices((co / 64) * (ci / 64), (T + WG_TC - 1) / WG_TC, 8);
+    return (size_t)(S + slab_groups(S)) * co * ci * 16 * sizeof(float);
 }
 
 static size_t wgrad_v2_ws(int n, int ci, int co, int h, int w_img) {
     const int64_t T = (int64_t)n * (h / 2) * (w_img / 2);
-    const int S = wgrad2_slices((co / 64) * (ci / 64), T / 16);
-    return (size_t)(S + wgrad_groups(S)) * co * ci * 9 * sizeof(float);
+    const int S = slab_slices((co / 64) * (ci / 64), T / 16, 4);   // 4 chunks: 64 tiles
+    return (size_t)(S + slab_groups(S)) * co * ci * 9 * sizeof(float);
 }
 
 extern "C" size_t smmd_wino3x3_wgrad_workspace_bytes(int n, int ci, int co, int h, int w_img) {
@@ -735,7 +679,7 @@ static smmd_status wgrad3_launch(const float *x, const float *gy, float *gw, int
     if (!ws || ws_bytes < smmd_wino3x3_wgrad_workspace_bytes(n, ci, co, h, w_img))
         return SMMD_EWORKSPACE;
     if (reinterpret_cast<uintptr_t>(ws) & 15) return SMMD_EINVAL;
-    WgGeom g;
+    WgGeom g{};
     g.N = n; g.C = ci; g.K = co; g.H = h; g.W = w_img;
     g.TW = w_img / 2;
     g.Timg = (h / 2) * g.TW;
@@ -747,36 +691,20 @@ static smmd_status wgrad3_launch(const float *x, const float *gy, float *gw, int
     const int ct = wgrad_v1_forced() ? 0 : wgrad2_ct(h, w_img);
     if (ct) {
         const int64_t nchunks = g.T / 16;
-        const int S = wgrad2_slices(blocks, nchunks);
+        const int S = slab_slices(blocks, nchunks, 4);
         g.chunks_per_slice = (int)((nchunks + S - 1) / S);
         const int Sused = (int)((nchunks + g.chunks_per_slice - 1) / g.chunks_per_slice);
         e = ct == 16 ? wgrad2_launch<16>(x, gy, part, g, Sused, st)
             : ct == 8 ? wgrad2_launch<8>(x, gy, part, g, Sused, st)
                       : wgrad2_launch<4>(x, gy, part, g, Sused, st);
         if (e != SMMD_OK) return e;
-        const int64_t nf4 = nkc * 9 / 4;
-        const int ng = wgrad_groups(Sused);
-        int Sfin = Sused;
-        if (ng > 0) {                              // two levels: groups of WG_GROUP slices, in order
-            float *grp = part + (size_t)S * nkc * 9;
-            const int64_t nt = nf4 * ng;
-            wino_wgrad_group_kernel<<<dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st>>>(
-                reinterpret_cast<const float4 *>(part), Sused, WG_GROUP, nf4, ng,
-                reinterpret_cast<float4 *>(grp));
-            e = last_launch_status();
-            if (e != SMMD_OK) return e;
-            part = grp;
-            Sfin = ng;
-        }
-        wino_wgrad_sum_kernel<<<dim3((unsigned)((nf4 + 255) / 256)), dim3(256), 0, st>>>(
-            reinterpret_cast<const float4 *>(part), Sfin, nf4, reinterpret_cast<float4 *>(gw),
-            acc);
-        return last_launch_status();
+        // the slices' dW partials, straight into dW
+        return slab_sum<for_wino3x3_wgrad>(part, Sused, S, nkc * 9 / 4, gw, acc, st);
     }
     const int64_t nchunks = (g.T + WG_TC - 1) / WG_TC;
-    const int S = wgrad_slices(blocks, nchunks);
+    const int S = slab_slices(blocks, nchunks, 8);
     g.chunks_per_slice = (int)((nchunks + S - 1) / S);
-    const int Sused = (int)((nchunks + g.chunks_per_slice - 1) / g.chunks_per_slice);
+    int Sused = (int)((nchunks + g.chunks_per_slice - 1) / g.chunks_per_slice);
     static bool attr = false;
     if (!attr) {
         if (hipFuncSetAttribute(reinterpret_cast<const void *>(wino_wgrad_kernel),
@@ -789,19 +717,12 @@ static smmd_status wgrad3_launch(const float *x, const float *gy, float *gw, int
                         WG_LDS, st>>>(x, gy, part, g);
     e = last_launch_status();
     if (e != SMMD_OK) return e;
-    const int ng = wgrad_groups(Sused);
-    if (ng > 0) {                                  // two-level: groups of WG_GROUP slices, in order
-        float *grp = part + (size_t)S * co * ci * 16;
-        const int64_t nf4 = nkc * 4, nt = nf4 * ng;
-        wino_wgrad_group_kernel<<<dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st>>>(
-            reinterpret_cast<const float4 *>(part), Sused, WG_GROUP, nf4, ng,
-            reinterpret_cast<float4 *>(grp));
-        e = last_launch_status();
-        if (e != SMMD_OK) return e;
-        part = grp;
-    }
+    // the slices' dU partials: the group level if there are many, then the
+    // sum with G^T . G
+    e = slab_group_level<for_wino3x3_wgrad>(part, Sused, S, nkc * 4, st);
+    if (e != SMMD_OK) return e;
     wino_wgrad_final_kernel<<<dim3((unsigned)((nkc + 255) / 256)), dim3(256), 0, st>>>(
-        part, ng > 0 ? ng : Sused, co, ci, gw, acc);
+        part, Sused, co, ci, gw, acc);
     return last_launch_status();
 }
 

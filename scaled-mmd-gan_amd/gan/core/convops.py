@@ -806,8 +806,7 @@ def _fwd(x, w, b, stride, padding, ymask=None, into=None):
             return _s2_conv(x, w, b, into)
         return into.add_(_fwd(x, w, b, stride, padding))
     if ymask is not None:
-        if (_is_wino(x, w, stride, padding, 0) and ymask.is_contiguous()
-                and os.environ.get('SMMD_WINO8', '1') != '0'):
+        if _is_wino(x, w, stride, padding, 0) and ymask.is_contiguous():
             return _wino_conv(x, w, b, 0, mask=ymask)
         return _aten.threshold_backward(_fwd(x, w, b, stride, padding), ymask, 0.0)
     if _is_thin(x, w, stride, padding):

@@ -52,6 +52,11 @@ def test_workspace_sizing(L):
     assert L.smmd_sn_workspace_bytes(arr, 2) > 16 * 4608 * 4
     offs = (ctypes.c_int64 * 3)(0, 10, 70000)
     assert L.smmd_opt_workspace_bytes(offs, 2) >= 8 * 6
+    # the weight gradients' slice partials, and past 32 slices the scratch of
+    # the group level behind them: 36 slices in groups of 16 / 16 / 4 (stride
+    # 2), 33 in 16 / 16 / 1 (3x3, tile rows of 6: the first form's dU slabs)
+    assert L.smmd_wino4x4s2_wgrad_workspace_bytes(9, 16, 64, 64, 64) == (36 + 3) * 64 * 16 * 16 * 4
+    assert L.smmd_wino3x3_wgrad_workspace_bytes(8, 64, 64, 88, 12) == (33 + 3) * 64 * 64 * 16 * 4
 
 
 def test_argument_validation_without_gpu(L):

@@ -25,10 +25,13 @@ def _check(fn, shape_w, seed):
     assert again is acc and torch.equal(acc, (base + plain) + plain)
 
 
-# (N, ci, co, H): the generator's / critic's first layers at batch 64, small
+# (N, ci, co, H[, W = H]): the generator's / critic's first layers at batch
+# 64, small; the last of WINO and of S2 add their slices in two levels (33 and
+# 36 slices: test_gpu_wino.WGRAD_SHAPES, test_gpu_wino_s2.S2_WGRAD_SHAPES)
 THIN = [(64, 3, 64, 64), (4, 3, 64, 16), (64, 64, 3, 64)]
-WINO = [(64, 64, 64, 32), (64, 512, 512, 8), (4, 128, 64, 16), (2, 64, 128, 8)]
-S2 = [(64, 64, 128, 64), (64, 512, 512, 8), (4, 64, 128, 16)]
+WINO = [(64, 64, 64, 32), (64, 512, 512, 8), (4, 128, 64, 16), (2, 64, 128, 8),
+        (8, 64, 64, 88, 12)]
+S2 = [(64, 64, 128, 64), (64, 512, 512, 8), (4, 64, 128, 16), (9, 16, 64, 64, 64)]
 C1 = [(64, 64, 128, 32), (64, 512, 1024, 4), (4, 128, 256, 8)]
 
 
@@ -46,20 +49,22 @@ def test_thin_wgrad_acc(shape):
 @pytest.mark.parametrize('shape', WINO)
 def test_wino_wgrad_acc(shape):
     from gan.core import convops
-    N, ci, co, H = shape
+    N, ci, co, H = shape[:4]
+    W = shape[4] if len(shape) > 4 else H
     g = torch.Generator(device=DEV).manual_seed(ci + co + H + 1)
-    x = torch.randn(N, ci, H, H, device=DEV, generator=g)
-    gy = torch.randn(N, co, H, H, device=DEV, generator=g)
+    x = torch.randn(N, ci, H, W, device=DEV, generator=g)
+    gy = torch.randn(N, co, H, W, device=DEV, generator=g)
     _check(lambda into: convops._wino_wgrad(x, gy, into), (co, ci, 3, 3), H + 1)
 
 
 @pytest.mark.parametrize('shape', S2)
 def test_s2_wgrad_acc(shape):
     from gan.core import convops
-    N, ci, co, H = shape
+    N, ci, co, H = shape[:4]
+    W = shape[4] if len(shape) > 4 else H
     g = torch.Generator(device=DEV).manual_seed(ci + co + H + 2)
-    x = torch.randn(N, ci, H, H, device=DEV, generator=g)
-    gy = torch.randn(N, co, H // 2, H // 2, device=DEV, generator=g)
+    x = torch.randn(N, ci, H, W, device=DEV, generator=g)
+    gy = torch.randn(N, co, H // 2, W // 2, device=DEV, generator=g)
     assert convops._s2_wgrad_ok(x, gy, co)
     _check(lambda into: convops._s2_wgrad(x, gy, into), (co, ci, 4, 4), H + 2)
 

@@ -70,37 +70,29 @@ def test_wino_forward_and_input_grad_vs_float64(shape):
 
 
 @pytest.mark.parametrize('shape', SHAPES)
-def test_wino_eight_wave_form_bit_identical(shape, monkeypatch):
-    """The 8-wave kernel (two waves per SIMD splitting the 16 points) and the
-    4-wave one accumulate every point in the same order and share the output
-    transform's arithmetic: the same bits, both modes, relu too."""
+def test_wino_relu_epilogue_is_clamp_of_conv(shape):
+    """smmd_wino3x3_conv_relu is max(conv + bias, 0) of smmd_wino3x3_conv's own
+    bits, where the ReLU runs in the kernel's epilogue and where it runs in
+    the split-channel slab reduction ((4, 512, 64, 8, 8), (8, 512, 512, 8, 8))."""
     from gan.core import _lib
     N, C, K, H, W = shape
     g = torch.Generator(device=DEV).manual_seed(N * 31 + C + K + H + W)
     x = torch.randn(N, C, H, W, device=DEV, generator=g)
     w = torch.randn(K, C, 3, 3, device=DEV, generator=g)
     b = torch.randn(K, device=DEV, generator=g)
-    out = {}
-    for form in ('0', '1'):
-        monkeypatch.setenv('SMMD_WINO8', form)
-        y0, _ = _abi_conv(x, w, b, 0)
-        y1, _ = _abi_conv(x, w.transpose(0, 1).contiguous(), None, 1) if C == K else (None, 0)
-        L = _lib.lib()
-        u = torch.empty(L.smmd_wino3x3_filter_bytes(K, C) // 4, device=DEV)
-        assert L.smmd_wino3x3_filter(_lib.ptr(w), K, C, 0, _lib.ptr(u), u.numel() * 4,
-                                     _lib.stream_handle()) == 0
-        yr = torch.empty(N, K, H, W, device=DEV)
-        nb = L.smmd_wino3x3_workspace_bytes(N, C, K, H, W)
-        ws = torch.empty(max(nb // 4, 1), device=DEV)
-        assert L.smmd_wino3x3_conv_relu(_lib.ptr(x), _lib.ptr(u), _lib.ptr(b), _lib.ptr(yr), N, C,
-                                        K, H, W, _lib.ptr(ws) if nb else None, nb,
-                                        _lib.stream_handle()) == 0
-        out[form] = (y0, y1, yr)
-    monkeypatch.delenv('SMMD_WINO8')
-    for a, c in zip(out['0'], out['1']):
-        if a is not None:
-            assert torch.equal(a, c)
-    assert (out['1'][2] >= 0).all()
+    y, _ = _abi_conv(x, w, b, 0)
+    L = _lib.lib()
+    u = torch.empty(L.smmd_wino3x3_filter_bytes(K, C) // 4, device=DEV)
+    assert L.smmd_wino3x3_filter(_lib.ptr(w), K, C, 0, _lib.ptr(u), u.numel() * 4,
+                                 _lib.stream_handle()) == 0
+    yr = torch.empty(N, K, H, W, device=DEV)
+    nb = L.smmd_wino3x3_workspace_bytes(N, C, K, H, W)
+    ws = torch.empty(max(nb // 4, 1), device=DEV)
+    assert L.smmd_wino3x3_conv_relu(_lib.ptr(x), _lib.ptr(u), _lib.ptr(b), _lib.ptr(yr), N, C,
+                                    K, H, W, _lib.ptr(ws) if nb else None, nb,
+                                    _lib.stream_handle()) == 0
+    assert (yr >= 0).all()
+    assert torch.equal(yr, y.clamp_min(0))
 
 
 def test_wino_split_channels_deterministic():
@@ -237,11 +229,12 @@ def wgrad_on():
 # the r11 kernel's chunk shapes: 16-tile rows with halo columns (W 64, 128),
 # whole 16-tile rows (W 32), two 8-tile rows (W 16), four 4-tile rows (W 8);
 # shapes it does not tile (6 x 8, 4 x 12, 2 x 4, W 8 with H % 8 != 0) take the
-# first form
+# first form; 88 x 12 (tile rows of 6) takes it with 33 slices, past the 32
+# from which the slices are added in two levels (groups of 16 / 16 / 1)
 WGRAD_SHAPES = [(2, 64, 64, 6, 8), (3, 64, 128, 8, 8), (4, 128, 64, 4, 12), (2, 64, 64, 2, 4),
                 (8, 64, 64, 64, 64), (8, 512, 512, 8, 8), (2, 64, 128, 32, 32),
                 (3, 128, 64, 16, 16), (1, 64, 64, 8, 128), (2, 64, 64, 12, 8),
-                (4, 128, 128, 32, 32), (16, 256, 256, 16, 16)]
+                (4, 128, 128, 32, 32), (16, 256, 256, 16, 16), (8, 64, 64, 88, 12)]
 
 
 @pytest.mark.parametrize('shape', WGRAD_SHAPES)

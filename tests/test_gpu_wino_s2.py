@@ -126,10 +126,13 @@ def test_conv_transpose_s2_autograd_vs_float64():
 
 # the critic's four folded ConvMeanPool layers (SNResNet-64: 64 -> 128 at 64 x 64
 # ... 512 -> 1024 at 8 x 8) at small batches, other tile grids, and shapes the
-# kernel does not tile (MIOpen then): (x [n, ci, h, w], co)
+# kernel does not tile (MIOpen then): (x [n, ci, h, w], co); one (k, c) block
+# over 144 chunks: 36 slices, past the 32 from which the slices are added in
+# two levels (groups of 16 / 16 / 4)
 S2_WGRAD_SHAPES = [(2, 64, 128, 64, 64), (2, 128, 256, 32, 32), (4, 256, 512, 16, 16),
                    (4, 512, 1024, 8, 8), (3, 16, 64, 32, 64), (2, 32, 64, 16, 32),
-                   (8, 16, 64, 16, 16), (2, 64, 64, 8, 8), (1, 16, 64, 12, 20)]
+                   (8, 16, 64, 16, 16), (2, 64, 64, 8, 8), (1, 16, 64, 12, 20),
+                   (9, 16, 64, 64, 64)]
 
 
 @pytest.mark.parametrize('shape', S2_WGRAD_SHAPES)

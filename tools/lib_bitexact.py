@@ -2,9 +2,8 @@
 for changes that must not move a single bit (block orders, the LDS-DMA wait
 placement): python tools/lib_bitexact.py LIB_A LIB_B
 
-Covered: the 3x3 conv over every tests/test_gpu_wino.py shape in both forms
-(8-wave default, SMMD_WINO8=0 the 4-wave one), modes 0 and 1 of the filter,
-the relu epilogue and the pair form; the stride-2 conv (plain and pair) and
+Covered: the 3x3 conv over every tests/test_gpu_wino.py shape, modes 0 and 1
+of the filter, the relu epilogue and the pair form; the stride-2 conv (plain and pair) and
 the transposed stride-2 conv over the fold-layer shapes; both weight
 gradients (3x3, stride 2) over their test shapes and the bench layers.  `make -C scaled-mmd-gan_amd/csrc conservative` builds
 the conservative variant (every filter-stage LDS-DMA piece waited for right
@@ -134,21 +133,18 @@ def main():
     st = _lib.stream_handle(dev)
     ok = True
     w3, w3pair = _w3_shapes()
-    for form in ('1', '0'):
-        os.environ['SMMD_WINO8'] = form          # read by the library at every call
-        for pair, shapes in ((False, w3), (True, w3pair)):
-            for (N, C, K, H, W) in shapes:
-                g = torch.Generator(device=dev).manual_seed(N + C + K + H + W)
-                x, x2 = (torch.randn(N, C, H, W, device=dev, generator=g) for _ in range(2))
-                w, w2 = (torch.randn(K, C, 3, 3, device=dev, generator=g) for _ in range(2))
-                b = torch.randn(K, device=dev, generator=g)
-                ra = run_w3(A, x, w, b, x2, w2, st, pair)
-                rb = run_w3(B, x, w, b, x2, w2, st, pair)
-                same = all(torch.equal(p, q) for p, q in zip(ra, rb))
-                ok &= same
-                print('3x3', 'wino8' if form == '1' else 'wino4', 'pair' if pair else 'conv',
-                      (N, C, K, H, W), 'bit-identical' if same else 'DIFFERENT', flush=True)
-    os.environ.pop('SMMD_WINO8', None)
+    for pair, shapes in ((False, w3), (True, w3pair)):
+        for (N, C, K, H, W) in shapes:
+            g = torch.Generator(device=dev).manual_seed(N + C + K + H + W)
+            x, x2 = (torch.randn(N, C, H, W, device=dev, generator=g) for _ in range(2))
+            w, w2 = (torch.randn(K, C, 3, 3, device=dev, generator=g) for _ in range(2))
+            b = torch.randn(K, device=dev, generator=g)
+            ra = run_w3(A, x, w, b, x2, w2, st, pair)
+            rb = run_w3(B, x, w, b, x2, w2, st, pair)
+            same = all(torch.equal(p, q) for p, q in zip(ra, rb))
+            ok &= same
+            print('3x3', 'pair' if pair else 'conv', (N, C, K, H, W),
+                  'bit-identical' if same else 'DIFFERENT', flush=True)
     for (N, C, K, H, W) in S2_SHAPES:
         g = torch.Generator(device=dev).manual_seed(N + C + K + H + W)
         x, x2 = (torch.randn(N, C, H, W, device=dev, generator=g) for _ in range(2))

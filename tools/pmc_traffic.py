@@ -17,6 +17,7 @@ from collections import defaultdict
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from stamp import library_stamp  # noqa: E402
 
+_TAG = 'smmd::(anonymous namespace)::for_%s>'     # a slab reduction's template argument
 GROUPS = {
     'smmd_sn_power_iter': ('sn_p1_kernel', 'sn_p2_kernel', 'sn_r2_kernel', 'sn_p3_kernel'),
     'smmd_sn_weight_bwd': ('sn_bwd_a_kernel', 'sn_bwd_b_kernel'),
@@ -38,14 +39,21 @@ GROUPS = {
     'smmd_conv3x3_thin': ('thin_in_kernel', 'thin_out_kernel'),
     'smmd_conv3x3_thin_wgrad': ('thin_wgrad_mfma_kernel', 'thin_wgrad_kernel',
                                 'thin_wgrad_final_kernel'),
-    'smmd_wino3x3_conv': ('wino_conv_kernel', 'wino_conv8_kernel', 'wino_reduce_kernel'),
+    # (the slab reductions of smmd_wino_common.hpp: one instance per entry
+    # point, told apart by their tag type)
+    'smmd_wino3x3_conv': ('wino_conv8_kernel', 'slab_reduce_bias_kernel<' + _TAG % 'wino3x3_conv'),
     'smmd_wino3x3_filter': ('wino_filter_kernel',),
-    'smmd_wino3x3_wgrad': ('wino_wgrad_kernel', 'wino_wgrad2_kernel', 'wino_wgrad_group_kernel',
-                           'wino_wgrad_final_kernel', 'wino_wgrad_sum_kernel'),
-    'smmd_wino4x4s2_conv': ('s2_conv_kernel',),
-    'smmd_wino4x4s2t_conv': ('s2t_conv_kernel',),
+    'smmd_wino3x3_wgrad': ('wino_wgrad_kernel', 'wino_wgrad2_kernel',
+                           'slab_group_kernel<' + _TAG % 'wino3x3_wgrad',
+                           'wino_wgrad_final_kernel',
+                           'slab_sum_kernel<' + _TAG % 'wino3x3_wgrad'),
+    'smmd_wino4x4s2_conv': ('s2_conv_kernel',
+                            'slab_reduce_bias_kernel<' + _TAG % 'wino4x4s2_conv'),
+    'smmd_wino4x4s2t_conv': ('s2t_conv_kernel',
+                             'slab_reduce_bias_kernel<' + _TAG % 'wino4x4s2t_conv'),
     'smmd_wino4x4s2_filter': ('s2_filter_kernel', 's2t_filter_kernel'),
-    'smmd_wino4x4s2_wgrad': ('s2_wgrad_kernel', 's2w_sum_kernel', 's2w_group_kernel'),
+    'smmd_wino4x4s2_wgrad': ('s2_wgrad_kernel', 'slab_sum_kernel<' + _TAG % 'wino4x4s2_wgrad',
+                             'slab_group_kernel<' + _TAG % 'wino4x4s2_wgrad'),
     'smmd_sn_clip_g': ('sn_clip_g_kernel',),
 }
 # entry points whose calls each run ONE of their kernels (fold or adjoint;

@@ -33,29 +33,6 @@ def timed(fn, iters):
     return e0.elapsed_time(e1) / iters * 1e3
 
 
-def clock_ghz(L, blocks):
-    """Diagnostic builds (-DWN_CLOCK) only: the median in-kernel clock of the
-    last launch's blocks, d(s_memtime) / d(s_memrealtime) x 100 MHz, and the
-    median block duration in us."""
-    if not hasattr(L, 'smmd_diag_wino_clock'):
-        return None
-    import ctypes
-    n = min(blocks, 4096)
-    buf = (ctypes.c_ulonglong * (4 * n))()
-    torch.cuda.synchronize()
-    if L.smmd_diag_wino_clock(buf, n) != 0:
-        return None
-    ghz, dur = [], []
-    for b in range(n):
-        t0, t1, r0, r1 = buf[4 * b:4 * b + 4]
-        if r1 > r0 and t1 > t0:
-            ghz.append((t1 - t0) / (r1 - r0) * 0.1)
-            dur.append((r1 - r0) / 100.0)
-    ghz.sort()
-    dur.sort()
-    return [round(ghz[len(ghz) // 2], 3), round(dur[len(dur) // 2], 2)] if ghz else None
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=50)
@@ -92,9 +69,8 @@ def main():
                                         K, H, H, _lib.ptr(ws), nb, st)
                 assert s == 0
             us = timed(f, a.iters)
-            clk = clock_ghz(L, N * (H // 2) ** 2 // 64 * (K // 64))
             fl = 2.0 * 16 * N * (H // 2) ** 2 * C * K
-            out['3x3_%d_%d_%d' % (C, K, H)] = {'us': round(us, 2), 'clock_ghz': clk,
+            out['3x3_%d_%d_%d' % (C, K, H)] = {'us': round(us, 2),
                                                'executed_tflops': round(fl / us / 1e6, 1),
                                                'mfma_frac': round(fl / us / 1e6 / 157.3, 3)}
             print(json.dumps({k: v for k, v in out.items() if k.startswith('3x3_%d_' % C)}),
