@@ -905,6 +905,54 @@ smmd_status smmd_conv1x1_wgrad_acc(const float *gy, const float *x, float *gw, i
                                    int k, int p, void *ws, size_t ws_bytes,
                                    smmd_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * The loss side of the GAN and WGAN-GP baselines (gan/core/gan.py,
+ * gan/core/wgan_gp.py).  fp32, one launch each, fixed-order reductions (no
+ * float atomics: two runs give the same bits).
+ *
+ * smmd_gp_interp: the gradient penalty's interpolates over b dense rows of
+ *   `per` floats (a sample in either memory format), alpha [b]:
+ *   form 0: out = real + alpha (fake - real)        (wgan_gp.py:13-14)
+ *   form 1: out = (1 - alpha) real + alpha fake     (cramer.py:78,
+ *           model.py:333-334).
+ *   Each operation rounds on its own, in the order written.
+ * smmd_gp_slope_fwd: g [b, c, h, w] (hw = h * w), the critic's input
+ *   gradient, NCHW-contiguous or (channels_last != 0) channels-last storage.
+ *   slopes [b * hw] in (b, h, w) order: sqrt(sum_c g^2 + eps); out [1] =
+ *   mean((slopes - 1)^2).  Replaces wgan_gp.py:18-19 (tf.sqrt of the
+ *   reduce_sum over axis 1: eps = 0); eps = 1e-8 is safer_norm
+ *   (ops.py:203-206, the witness penalty model.py:341-343).  Workspace from
+ *   smmd_gp_slope_workspace_bytes, zero at first use (the arrival ticket).
+ * smmd_gp_slope_bwd: dg = go[0] * 2 (s - 1) / (s n) * g in g's layout, n =
+ *   b * hw, go a device scalar: TF's autodiff of wgan_gp.py:18-19.  At s == 0
+ *   with eps == 0 the formula's IEEE result (NaN) stands, as tf.sqrt's
+ *   gradient gives.
+ * smmd_critic_head_fwd: critic outputs d_real [n_real], d_fake [n_fake].
+ *   kind 0 (wgan_gp.py:24-25): out[0] = mean(fake) - mean(real),
+ *           out[1] = -mean(fake).
+ *   kind 1 (gan.py:10-11): out[0] = mean(softplus(-real)) + mean(softplus(
+ *           fake)), out[1] = mean(softplus(-fake)), softplus(x) = max(x, 0) +
+ *           log1p(exp(-|x|)).
+ *   The row gradients in the same launch: g_real = d out[0] / d real,
+ *   g_fake = d out[0] / d fake, gg_fake = d out[1] / d fake (all required).
+ * ------------------------------------------------------------------------- */
+smmd_status smmd_gp_interp(const float *real, const float *fake, const float *alpha, float *out,
+                           int b, int64_t per, int form, smmd_stream_t stream);
+
+size_t smmd_gp_slope_workspace_bytes(int b, int c, int hw);
+
+smmd_status smmd_gp_slope_fwd(const float *g, int b, int c, int hw, int channels_last, float eps,
+                              float *out, float *slopes, void *ws, size_t ws_bytes,
+                              smmd_stream_t stream);
+
+smmd_status smmd_gp_slope_bwd(const float *g, const float *slopes, int b, int c, int hw,
+                              int channels_last, const float *go, float *dg,
+                              smmd_stream_t stream);
+
+smmd_status smmd_critic_head_fwd(const float *d_real, int n_real, const float *d_fake, int n_fake,
+                                 int kind, float *out, float *g_real, float *g_fake,
+                                 float *gg_fake, smmd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

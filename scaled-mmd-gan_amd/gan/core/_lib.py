@@ -200,6 +200,11 @@ _SIGS = {
     'smmd_poly_diff_ratio': (_I, [ctypes.POINTER(PolySums), ctypes.POINTER(PolySums),
                                   ctypes.POINTER(PolySums), ctypes.POINTER(PolySums), _I, _P,
                                   _P]),
+    'smmd_gp_interp': (_I, [_P, _P, _P, _P, _I, _I64, _I, _P]),
+    'smmd_gp_slope_workspace_bytes': (_SZ, [_I, _I, _I]),
+    'smmd_gp_slope_fwd': (_I, [_P, _I, _I, _I, _I, _F, _P, _P, _P, _SZ, _P]),
+    'smmd_gp_slope_bwd': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    'smmd_critic_head_fwd': (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -1125,11 +1125,17 @@ def _shared_gy_key(ctx):
     summed by autograd into one input of that producer, which runs after both
     -- or None outside an armed backward.  The producer node is kept alive by
     the entry (_late['gy'], cleared by arm_late_wgrad_sums), so its id is not
-    reused while the key stands."""
+    reused while the key stands.  Only a custom Function's node (_ReluPool's):
+    that object IS the node.  A built-in node is handed out as a wrapper made
+    per access, whose id another node's wrapper can take once it is freed --
+    a plain residual critic (ResNetDiscriminator) then matched a 4x4 gradient
+    with a 64x64 one."""
     if not (GY_ACC and _late['armed']) or torch.is_grad_enabled():
         return None
     fn, nr = ctx.next_functions[2]
-    return None if fn is None else (id(fn), nr)
+    if not isinstance(fn, torch.autograd.function.BackwardCFunction):
+        return None
+    return (id(fn), nr)
 
 
 def _late_target(w):

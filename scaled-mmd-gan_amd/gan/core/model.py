@@ -196,6 +196,11 @@ class MMD_GAN:
     def sample_z(self, n):
         return torch.empty(n, self.z_dim, device=self.device).uniform_(-1.0, 1.0)  # model.py:271
 
+    def sample_alpha(self, n):
+        """The interpolation weights of a gradient penalty, one per sample
+        (wgan_gp.py:10)."""
+        return torch.rand(n, 1, 1, 1, device=self.device)
+
     # ------------------------------------------------------------------
     # the reference's loss hooks (model.py:268-403; SMMD / SWGAN override
     # set_loss and apply_scaling, smmd.py:10-42).  They work on the same

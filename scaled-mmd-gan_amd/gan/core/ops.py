@@ -7,8 +7,13 @@
   ``apply_scaling`` (gan/core/smmd.py:21-23, :40-42) in libsmmd_hip: one
   HBM pass over the input-gradient, one single-block finalize, and a one-pass
   backward that feeds PyTorch's double-backward through the critic.
+* ``gp_interpolate`` / ``slope_penalty`` / ``critic_head_loss``: the loss side
+  of the GAN and WGAN-GP baselines (gan/core/gan.py:10-11,
+  gan/core/wgan_gp.py:10-25), one HIP launch forward and one backward each.
 """
 from __future__ import annotations
+
+import os
 
 import torch
 import torch.distributed as dist
@@ -298,3 +303,164 @@ class _SqNormJac(torch.autograd.Function):
 def squared_norm_jacobian(y, x):
     """sum_i ||d y[:, i] / d x||^2 per sample  (gan/core/ops.py:228-233)."""
     return _SqNormJac.apply(jacobian_columns(y, x))
+
+
+# ---------------------------------------------------------------------------
+# the loss side of the GAN / WGAN-GP baselines (csrc/smmd_gp.hip): one launch
+# forward and one backward each.  SMMD_GP_FUSED=0 routes them through plain
+# tensor ops in the same arithmetic order (A/B); CPU or non-fp32 tensors take
+# that path too, so the models also build without a GPU.
+# ---------------------------------------------------------------------------
+GP_FUSED = os.environ.get('SMMD_GP_FUSED', '1') != '0'
+
+
+def _gp_fused(*tensors):
+    return GP_FUSED and all(t.is_cuda and t.dtype == torch.float32 for t in tensors)
+
+
+def _is_channels_last(t):
+    return (t.dim() == 4 and not t.is_contiguous()
+            and t.is_contiguous(memory_format=torch.channels_last))
+
+
+def gp_interpolate(real, fake, alpha, form=0):
+    """The gradient penalty's interpolates between two batches, alpha one
+    number per sample ([b] or [b, 1, 1, 1]): form 0 is real + alpha * (fake -
+    real) (wgan_gp.py:13-14), form 1 (1 - alpha) * real + alpha * fake
+    (cramer.py:78, model.py:333-334).  Not differentiable (every caller
+    detaches both batches); returns a new tensor in ``real``'s memory format,
+    ready to be made a leaf."""
+    if form not in (0, 1):
+        raise ValueError('form must be 0 or 1')
+    real, fake, alpha = real.detach(), fake.detach(), alpha.detach()
+    b = real.shape[0]
+    if fake.shape != real.shape or alpha.numel() != b:
+        raise ValueError('gp_interpolate: real %s, fake %s, alpha %s'
+                         % (tuple(real.shape), tuple(fake.shape), tuple(alpha.shape)))
+    if not _gp_fused(real, fake, alpha):
+        a = alpha.reshape([b] + [1] * (real.dim() - 1))
+        if form == 0:
+            return real + a * (fake - real)
+        return (1.0 - a) * real + a * fake
+    # dense rows either way: the kernel is told only the row length
+    fmt = torch.channels_last if _is_channels_last(real) else torch.contiguous_format
+    real = real.contiguous(memory_format=fmt)
+    fake = fake.contiguous(memory_format=fmt)
+    alpha = alpha.reshape(b).contiguous()
+    out = torch.empty_like(real)
+    per = real.numel() // b
+    _lib.add_bytes('smmd_gp_interp', 3 * real.numel() * 4)
+    with _lib.timed('smmd_gp_interp'):
+        st = _lib.lib().smmd_gp_interp(_lib.ptr(real), _lib.ptr(fake), _lib.ptr(alpha),
+                                       _lib.ptr(out), b, per, form,
+                                       _lib.stream_handle(real.device))
+    _lib.check(st, 'smmd_gp_interp')
+    return out
+
+
+class _SlopePenalty(torch.autograd.Function):
+    """mean over pixels of (sqrt(sum_c g^2 + eps) - 1)^2 for g [b, c, h, w];
+    the backward is one elementwise launch from the saved slopes."""
+
+    @staticmethod
+    def forward(ctx, g, eps):
+        cl = _is_channels_last(g)
+        if not cl:
+            g = g.contiguous()
+        b, c = g.shape[0], g.shape[1]
+        hw = g.numel() // (b * c)
+        dev = g.device
+        L = _lib.lib()
+        out = torch.empty(1, device=dev, dtype=torch.float32)
+        slopes = torch.empty(b * hw, device=dev, dtype=torch.float32)
+        nbytes = L.smmd_gp_slope_workspace_bytes(b, c, hw)
+        ws = _lib.workspace('gp_slope', nbytes, dev)
+        _lib.add_bytes('smmd_gp_slope_fwd', (g.numel() + slopes.numel()) * 4)
+        with _lib.timed('smmd_gp_slope_fwd'):
+            st = L.smmd_gp_slope_fwd(_lib.ptr(g), b, c, hw, int(cl), float(eps), _lib.ptr(out),
+                                     _lib.ptr(slopes), _lib.ptr(ws), ws.numel(),
+                                     _lib.stream_handle(dev))
+        _lib.check(st, 'smmd_gp_slope_fwd')
+        ctx.save_for_backward(g, slopes)
+        ctx.cfg = (b, c, hw, int(cl))
+        return out.view(())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, go):
+        g, slopes = ctx.saved_tensors
+        b, c, hw, cl = ctx.cfg
+        go = go.reshape(1).contiguous().to(torch.float32)
+        dg = torch.empty_like(g)                     # g's strides (dense)
+        _lib.add_bytes('smmd_gp_slope_bwd', (2 * g.numel() + slopes.numel()) * 4)
+        with _lib.timed('smmd_gp_slope_bwd'):
+            st = _lib.lib().smmd_gp_slope_bwd(_lib.ptr(g), _lib.ptr(slopes), b, c, hw, cl,
+                                              _lib.ptr(go), _lib.ptr(dg),
+                                              _lib.stream_handle(g.device))
+        _lib.check(st, 'smmd_gp_slope_bwd')
+        return dg, None
+
+
+def slope_penalty(g, eps=0.0):
+    """The gradient penalty of a critic input gradient g [b, c, h, w]:
+    mean((slopes - 1)^2), slopes = sqrt(sum over the channel axis of g^2 + eps)
+    per pixel (wgan_gp.py:18-19; eps 0 is its plain tf.sqrt, eps 1e-8
+    safer_norm).  A 0-dim tensor, differentiable once with respect to g: a
+    critic update needs dP/dg only, the rest of the chain being the critic's
+    own second-order rule.  The memory format is read from g's strides."""
+    if g.dim() < 2:
+        raise ValueError('slope_penalty expects [b, c, ...]')
+    if not _gp_fused(g):
+        s = torch.sqrt((g * g).sum(dim=1) + eps)
+        return torch.mean((s - 1.0) ** 2)
+    return _SlopePenalty.apply(g, float(eps))
+
+
+class _CriticHead(torch.autograd.Function):
+    """(d_base, g_loss) of the Wasserstein (kind 0) or softplus (kind 1) head
+    and, from the same launch, their row gradients; the backward scales them
+    by the upstream scalars."""
+
+    @staticmethod
+    def forward(ctx, d_real, d_fake, kind):
+        dev = d_real.device
+        xr = d_real.detach().reshape(-1).contiguous()
+        xf = d_fake.detach().reshape(-1).contiguous()
+        out = torch.empty(2, device=dev, dtype=torch.float32)
+        g_real = torch.empty_like(xr)
+        g_fake = torch.empty_like(xf)
+        gg_fake = torch.empty_like(xf)
+        with _lib.timed('smmd_critic_head_fwd'):
+            st = _lib.lib().smmd_critic_head_fwd(_lib.ptr(xr), xr.numel(), _lib.ptr(xf), xf.numel(),
+                                                 int(kind), _lib.ptr(out), _lib.ptr(g_real),
+                                                 _lib.ptr(g_fake), _lib.ptr(gg_fake),
+                                                 _lib.stream_handle(dev))
+        _lib.check(st, 'smmd_critic_head_fwd')
+        ctx.save_for_backward(g_real, g_fake, gg_fake)
+        ctx.shapes = (d_real.shape, d_fake.shape)
+        d_base, g_loss = out.unbind(0)
+        return d_base, g_loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, go_d, go_g):
+        g_real, g_fake, gg_fake = ctx.saved_tensors
+        sr, sf = ctx.shapes
+        return ((go_d * g_real).view(sr), (go_d * g_fake + go_g * gg_fake).view(sf), None)
+
+
+def critic_head_loss(d_real, d_fake, kind):
+    """The critic head on outputs [n, 1]: kind 0, WGAN (wgan_gp.py:24-25):
+    d_base = mean(d_fake) - mean(d_real), g_loss = -mean(d_fake); kind 1, GAN
+    (gan.py:10-11): d_base = mean(softplus(-d_real)) + mean(softplus(d_fake)),
+    g_loss = mean(softplus(-d_fake)).  Returns (d_base, g_loss), both 0-dim
+    and differentiable with respect to both critic outputs."""
+    if kind not in (0, 1):
+        raise ValueError('kind must be 0 (wgan) or 1 (gan)')
+    if not _gp_fused(d_real, d_fake):
+        if kind == 0:
+            mf = d_fake.mean()
+            return mf - d_real.mean(), -mf
+        sp = torch.nn.functional.softplus
+        return sp(-d_real).mean() + sp(d_fake).mean(), sp(-d_fake).mean()
+    return _CriticHead.apply(d_real, d_fake, kind)

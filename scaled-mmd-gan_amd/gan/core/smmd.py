@@ -73,15 +73,20 @@ class SWGAN(MMD_GAN):
 
 
 def get_model(name):
-    """Model dispatch of gan/main.py:139-152 (gan / wgan_gp / cramer are outside
-    this build)."""
+    """Model dispatch of gan/main.py:139-152 (cramer is outside this build)."""
     if name == 'mmd':
         return MMD_GAN
     if name == 'smmd':
         return SMMD
     if name == 'swgan':
         return SWGAN
-    if name in ('gan', 'wgan_gp', 'cramer'):
+    if name == 'gan':
+        from .gan import GAN
+        return GAN
+    if name == 'wgan_gp':
+        from .wgan_gp import WGAN_GP
+        return WGAN_GP
+    if name == 'cramer':
         raise NotImplementedError('model %r is outside this build (SURVEY.md section 2)' % name)
     raise ValueError('unknown model {}'.format(name))
 
