@@ -610,6 +610,45 @@ smmd_status smmd_bn_relu_bwd(const float *x, const float *gy, int N, int C, int 
                              float *gbeta, void *ws, size_t ws_bytes, smmd_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Class-conditional batch norm + ReLU (the conditional generator's up blocks):
+ * resnet/ops/cond_batchnorm.py:6-17 then tf.nn.relu (resnet/block.py:42-47,
+ * architecture.py:71-100).  Per channel the batch's mean and biased variance
+ * over (N, HW), no moving averages; per sample the rows labels[n] of the
+ * [num_classes, C] tables:
+ *   z[n, c, :] = (x - mean_c) inv_c scale[l_n, c] + offset[l_n, c],
+ *   inv_c = 1 / sqrt(var_c + eps),  y = relu(z).
+ * x, y [N, C, HW] NCHW fp32, 16-byte aligned, HW % 4 == 0; labels int32 [N] on
+ * the device, a value outside [0, num_classes) is clamped into the tables.
+ * Statistics as smmd_bn_relu_fwd (shifted sums in double, fixed order).
+ * save (NULL when no gradient is taken) [3 C] = per channel {k, mean - k,
+ * inv} (k: the channel's first element, the statistics' shift).  A NULL
+ * pointer, num_classes <= 0 or a workspace shorter than
+ * smmd_cond_bn_relu_workspace_bytes gives SMMD_EINVAL before any launch.
+ *
+ * smmd_cond_bn_relu_bwd: with z recomputed from x and save exactly as the
+ * forward formed it (the ReLU mask bit for bit), gz = gy [z > 0],
+ * xhat = (x - mean) inv, gamma[n, c] = scale[l_n, c], M = N HW:
+ *   a[n, c] = sum_hw gz,  b[n, c] = sum_hw gz xhat,
+ *   goffset[k, c] = sum_{n: l_n = k} a[n, c],  gscale[k, c] the same over b
+ *   (sample order; every row of both [num_classes, C] tables is written, zeros
+ *   for a class absent from the batch),
+ *   gx = inv (gamma gz - S1 / M - xhat S2 / M), S1 = sum_n gamma a,
+ *   S2 = sum_n gamma b.
+ * No atomics: two runs give the same bits.
+ * ------------------------------------------------------------------------- */
+size_t smmd_cond_bn_relu_workspace_bytes(int N, int C);
+
+smmd_status smmd_cond_bn_relu_fwd(const float *x, const int32_t *labels, int N, int C, int HW,
+                                  int num_classes, const float *scale, const float *offset,
+                                  float eps, float *y, float *save, void *ws, size_t ws_bytes,
+                                  smmd_stream_t stream);
+
+smmd_status smmd_cond_bn_relu_bwd(const float *x, const float *gy, const int32_t *labels, int N,
+                                  int C, int HW, int num_classes, const float *scale,
+                                  const float *offset, const float *save, float *gx, float *gscale,
+                                  float *goffset, void *ws, size_t ws_bytes, smmd_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Thin 3x3 convolutions: stride 1, zero padding 1 (TF SAME at stride 1), NCHW
  * fp32, one side with <= 4 channels.  They serve the critics' first layer
  * (3 -> dim: snops.conv2d / resnet Conv2D, gan/core/snops.py:69-90,

@@ -159,6 +159,10 @@ _SIGS = {
     'smmd_bn_relu_fwd': (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _F, _F, _P, _P, _SZ, _P]),
     'smmd_bn_relu_fwd_save': (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _F, _F, _P, _P, _P, _SZ, _P]),
     'smmd_bn_relu_bwd': (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    'smmd_cond_bn_relu_workspace_bytes': (_SZ, [_I, _I]),
+    'smmd_cond_bn_relu_fwd': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P, _SZ, _P]),
+    'smmd_cond_bn_relu_bwd': (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _SZ,
+                                   _P]),
     'smmd_conv3x3_thin_wgrad_workspace_bytes': (_SZ, [_I, _I, _I, _I, _I]),
     'smmd_conv3x3_thin_wgrad': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _SZ, _P]),
     'smmd_conv3x3_thin_wgrad_acc': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _SZ, _P]),

@@ -4,8 +4,9 @@ on PyTorch-ROCm, NCHW fp32.
 Built: sngan (SNGANGenerator + SNGANDiscriminator, cifar10_smmd.yml),
 snresnet (SNResNetGenerator + SNResNetDiscriminator, imagenet_smmd.yml),
 g-resnet5 (ResNetGenerator + DCGAN5Discriminator, celebA_smmd.yml), plus the
-plain dcgan / dcgan5 / sngan-dcgan5 / resnet5 variants.  The conditional
-(label) networks are out of scope.
+plain dcgan / dcgan5 / sngan-dcgan5 / resnet5 variants, and the
+class-conditional cond_snresnet (CondSNResNetGenerator +
+CondProjectionSNResNetDiscriminator, -with_labels true).
 """
 from __future__ import annotations
 
@@ -19,7 +20,8 @@ from . import convops
 from . import optim as _optim
 from .convops import (conv2d, conv_transpose_s2, fold_pool_weight, fold_pool_weights,
                       fold_up_weight, mean_pool2)
-from .snops import Conv2d, Deconv2d, Linear, batch_norm, bn_relu, lrelu
+from .snops import (CondBatchNorm2d, Conv2d, Deconv2d, Linear, LinearOneHot, batch_norm, bn_relu,
+                    cond_bn_relu, labels_int32, lrelu)
 
 
 def conv_sizes(size, layers, stride=2):
@@ -192,7 +194,7 @@ class ResidualBlock(nn.Module):
     """block.py:9-50: shortcut + conv_2(relu(norm(conv_1(relu(norm(x))))))."""
 
     def __init__(self, cin, cout, k=3, resample=None, mode='', with_sn=False,
-                 with_learnable_sn_scale=False):
+                 with_learnable_sn_scale=False, num_classes=None):
         super().__init__()
         sn = dict(with_sn=with_sn, with_learnable_sn_scale=with_learnable_sn_scale)
         if resample == 'down':
@@ -219,11 +221,18 @@ class ResidualBlock(nn.Module):
         else:
             self.shortcut = short(cin, cout, 1, True, **sn)
         use_bn = mode == 'batchnorm'                     # Normalize, block.py:76-86
-        self.bn1 = _bn_or_id(use_bn, n1)
-        self.bn2 = _bn_or_id(use_bn, n2)
+        if mode == 'cond_batchnorm':
+            if not num_classes or num_classes < 1:
+                raise ValueError("mode 'cond_batchnorm' needs num_classes")
+            self.bn1 = CondBatchNorm2d(num_classes, n1)
+            self.bn2 = CondBatchNorm2d(num_classes, n2)
+        else:
+            self.bn1 = _bn_or_id(use_bn, n1)
+            self.bn2 = _bn_or_id(use_bn, n2)
+        self._cond = mode == 'cond_batchnorm'
         # a critic down block: relu(x) (main path) and the shortcut's mean pool
         # of x read the input in one pass (convops.relu_pool)
-        self._relu_pool = resample == 'down' and not use_bn
+        self._relu_pool = resample == 'down' and not use_bn and not self._cond
         # an up block: the shortcut's upsample, both conv biases and the sum
         # in one pass (convops.up_add)
         self._up_add = resample == 'up' and isinstance(self.shortcut, _Up)
@@ -251,7 +260,12 @@ class ResidualBlock(nn.Module):
             return s, h, sc.bias, self.conv_2.conv.bias
         return sc(p), self.conv_2(h1, mask_in=fuse), None, None
 
-    def forward(self, x):
+    def _norm_relu(self, bn, x, y):
+        """relu(Normalize(x)) (block.py:42-47): the labels y (int32, see
+        snops.labels_int32) reach the conditional norms only."""
+        return cond_bn_relu(bn, x, y) if self._cond else bn_relu(bn, x)
+
+    def forward(self, x, y=None):
         if self._relu_pool and convops.relu_pool_applicable(x):
             s, h, _, _ = self.down_parts(x)
             return s + h
@@ -259,12 +273,12 @@ class ResidualBlock(nn.Module):
                 self.shortcut.conv.k == 1 and self.shortcut.conv.stride == 1:
             sc = self.shortcut.conv
             s = sc(x, with_bias=False)                   # 1x1 conv before the upsample
-            h = self.conv_1(bn_relu(self.bn1, x))
-            h = self.conv_2(bn_relu(self.bn2, h), with_bias=False)
+            h = self.conv_1(self._norm_relu(self.bn1, x, y))
+            h = self.conv_2(self._norm_relu(self.bn2, h, y), with_bias=False)
             return convops.up_add(s, sc.bias, h, self.conv_2.bias)
         s = x if self.shortcut is None else self.shortcut(x)
-        h = self.conv_1(bn_relu(self.bn1, x))
-        h = self.conv_2(bn_relu(self.bn2, h))
+        h = self.conv_1(self._norm_relu(self.bn1, x, y))
+        h = self.conv_2(self._norm_relu(self.bn2, h, y))
         return s + h
 
 
@@ -366,6 +380,40 @@ class SNResNetGenerator(nn.Module):
     def forward(self, z):
         h = self.h0_lin(z).view(-1, self.dim * 16, self.s32, self.s32)
         h = bn_relu(self.bn4, self.res(h))
+        return torch.sigmoid(self.h5(h))
+
+
+class CondSNResNetGenerator(nn.Module):
+    """architecture.py:71-100: SNResNetGenerator with mode='cond_batchnorm' up
+    blocks (res0_bis only when output_size != 64); the final norm g_h4 is the
+    unconditional batch norm, then the 3x3 deconv and the sigmoid."""
+
+    def __init__(self, num_classes, dim, c_dim, output_size, use_batch_norm, z_dim=128):
+        super().__init__()
+        s = conv_sizes(output_size, 5)
+        s32 = 4 if output_size == 64 else s[5]
+        self.num_classes, self.dim, self.s32 = int(num_classes), dim, s32
+        self.h0_lin = Linear(z_dim, dim * 16 * s32 * s32)
+        cond = dict(k=3, resample='up', mode='cond_batchnorm', num_classes=self.num_classes)
+        blocks = []
+        if output_size != 64:
+            blocks.append(ResidualBlock(16 * dim, 16 * dim, **cond))
+        blocks += [ResidualBlock(16 * dim, 8 * dim, **cond),
+                   ResidualBlock(8 * dim, 4 * dim, **cond),
+                   ResidualBlock(4 * dim, 2 * dim, **cond),
+                   ResidualBlock(2 * dim, dim, **cond)]
+        self.res = nn.ModuleList(blocks)
+        self.bn4 = batch_norm(dim)
+        self.h5 = Deconv2d(dim, c_dim, 3, 1)
+
+    def forward(self, z, y):
+        if y is None:
+            raise ValueError('CondSNResNetGenerator needs the labels')
+        y = labels_int32(y)          # once per forward, for every conditional norm
+        h = self.h0_lin(z).view(-1, self.dim * 16, self.s32, self.s32)
+        for b in self.res:
+            h = b(h, y)
+        h = bn_relu(self.bn4, h)
         return torch.sigmoid(self.h5(h))
 
 
@@ -492,6 +540,32 @@ class SNResNetDiscriminator(nn.Module):
         return u if slope == 1.0 else lrelu(u, slope)
 
 
+class CondProjectionSNResNetDiscriminator(SNResNetDiscriminator):
+    """architecture.py:291-320: the SN ResNet critic with a projection head.
+    With labels y, hF <- hF + sum_j (w_y * hF)_j, w_y the rows y of the
+    (spectrally normalised) class embedding (snops.py:208-228); without (the
+    witness penalty's call, model.py:335) the plain critic."""
+
+    def __init__(self, num_classes, dim, o_dim, use_batch_norm, with_sn=False,
+                 with_learnable_sn_scale=False, input_size=64):
+        super().__init__(dim, o_dim, use_batch_norm, with_sn=with_sn,
+                         with_learnable_sn_scale=with_learnable_sn_scale, input_size=input_size)
+        self.num_classes = int(num_classes)
+        self.embed = LinearOneHot(self.num_classes, o_dim, with_sn=with_sn,
+                                  with_learnable_sn_scale=with_learnable_sn_scale)
+
+    def forward(self, x, return_layers=False, y=None):
+        out = super().forward(x, return_layers)
+        if y is None:
+            return out
+        hF = out['hF'] if return_layers else out
+        hF = hF + (self.embed(y) * hF).sum(1, keepdim=True)
+        if return_layers:
+            out['hF'] = hF
+            return out
+        return hF
+
+
 class ResNetDiscriminator(nn.Module):
     """architecture.py:358-375 (no SN)."""
 
@@ -532,12 +606,14 @@ def get_networks(architecture):
         'sngan-dcgan5': (SNGANGenerator, lambda *a, **k: DCGANDiscriminator(*a, layers=5, **k)),
         'snresnet': (SNResNetGenerator, SNResNetDiscriminator),
         'resnet5': (ResNetGenerator, ResNetDiscriminator),
+        # both take num_classes first (architecture.py:57-60, :272-275)
+        'cond_snresnet': (CondSNResNetGenerator, CondProjectionSNResNetDiscriminator),
     }
     if architecture in gd:
         return gd[architecture]
     if 'g-resnet5' in architecture:
         return ResNetGenerator, lambda *a, **k: DCGANDiscriminator(*a, layers=5, **k)
-    if architecture in ('cond_snresnet', 'd-fullconv5', 'dc64', 'dcgan64', 'dc128'):
+    if architecture in ('d-fullconv5', 'dc64', 'dcgan64', 'dc128'):
         raise NotImplementedError('architecture %r is outside this build (SURVEY.md section 2)'
                                   % architecture)
     raise ValueError('Wrong architecture: "%s"' % architecture)

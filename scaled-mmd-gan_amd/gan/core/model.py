@@ -122,11 +122,26 @@ class MMD_GAN:
         self.c_dim = c_dim
         self.z_dim = c.z_dim
         self.timer = Timer()
+        # class-conditional training (model.py:81-83, :273-275): the labels
+        # and the conditional pair come together
+        self.with_labels = bool(getattr(c, 'with_labels', False))
+        if self.with_labels != (c.architecture == 'cond_snresnet'):
+            raise ValueError("with_labels and architecture 'cond_snresnet' go together (got "
+                             'with_labels=%s, architecture=%r)' % (self.with_labels, c.architecture))
+        self.num_classes = int(getattr(c, 'num_classes', 1000)) if self.with_labels else None
+        if self.with_labels:
+            if self.num_classes < 1:
+                raise ValueError('num_classes must be positive')
+            if dp_mode == 'global':
+                raise NotImplementedError(
+                    "conditional model: dp_mode='global' is not built (the all-gather carries "
+                    "the critic features only, not each rank's labels; use dp_mode='tower')")
         G_cls, D_cls = get_networks(c.architecture)
         dbn = bool(c.batch_norm) and (c.gradient_penalty <= 0)   # model.py:270
-        self.generator = G_cls(c.gf_dim, c_dim, self.output_size, c.batch_norm,
+        cond = (self.num_classes,) if self.with_labels else ()
+        self.generator = G_cls(*cond, c.gf_dim, c_dim, self.output_size, c.batch_norm,
                                z_dim=c.z_dim).to(self.device)
-        self.discriminator = D_cls(c.df_dim, c.dof_dim, dbn, with_sn=c.with_sn,
+        self.discriminator = D_cls(*cond, c.df_dim, c.dof_dim, dbn, with_sn=c.with_sn,
                                    with_learnable_sn_scale=c.with_learnable_sn_scale,
                                    input_size=self.output_size).to(self.device)
         self.memory_format = torch.channels_last if channels_last else torch.contiguous_format
@@ -196,6 +211,35 @@ class MMD_GAN:
     def sample_z(self, n):
         return torch.empty(n, self.z_dim, device=self.device).uniform_(-1.0, 1.0)  # model.py:271
 
+    def sample_y(self, n):
+        """The generated batch's labels, uniform over the classes
+        (model.py:282-283)."""
+        return torch.randint(0, self.num_classes, (n,), device=self.device)
+
+    def _generate(self, n):
+        """G(z) or, conditional, G(z, y): (fake, y), y None without labels."""
+        z = self.sample_z(n)
+        if not getattr(self, 'with_labels', False):
+            return self.generator(z), None
+        y = self.sample_y(n)
+        return self.generator(z, y), y
+
+    def _check_labels(self, labels):
+        """A conditional model's real batch comes with its labels (whose range
+        the pipeline checked on the host, pipeline.check_label_range; a host
+        tensor is checked here, a device one is not read back)."""
+        if not getattr(self, 'with_labels', False):
+            if labels is not None:
+                raise ValueError('labels given to a model built without with_labels')
+            return None
+        if labels is None:
+            raise ValueError('a conditional model (with_labels) needs the labels of the batch')
+        labels = torch.as_tensor(labels)
+        if not labels.is_cuda and labels.numel() and \
+                (int(labels.min()) < 0 or int(labels.max()) >= self.num_classes):
+            raise ValueError('label outside [0, %d)' % self.num_classes)
+        return labels.to(self.device)
+
     def sample_alpha(self, n):
         """The interpolation weights of a gradient penalty, one per sample
         (wgan_gp.py:10)."""
@@ -212,14 +256,24 @@ class MMD_GAN:
         """The group the loss spans: all ranks in the all-gather mode."""
         return self._dist_group() if self.dp_mode == 'global' else None
 
-    def set_tower_loss(self, images, fake, need_critic_grad):
+    def set_tower_loss(self, images, fake, need_critic_grad, labels=None, fake_labels=None):
         """The loss half of model.py:268-311: the critic on the real and the
         generated batch, then ``set_loss(self.d_G, self.d_images)``.
         ``need_critic_grad``: build the graph for d_loss w.r.t. the critic
-        (the Jacobian's double backward, the penalties).  Returns
-        (g_loss, d_loss, aux)."""
+        (the Jacobian's double backward, the penalties).  Conditional: the
+        critic sees ``labels`` with the real batch and ``fake_labels`` with the
+        generated one (model.py:297-301), kept as self.labels / self.y.
+        Returns (g_loss, d_loss, aux)."""
         D = self.discriminator
         c = self.config
+        if getattr(self, 'with_labels', False):
+            if labels is None or fake_labels is None:
+                raise ValueError('a conditional model (with_labels) needs the labels of the '
+                                 'real and of the generated batch')
+            self.labels, self.y = labels, fake_labels
+            real_kw, fake_kw = dict(y=labels), dict(y=fake_labels)
+        else:
+            real_kw = fake_kw = {}
         if images.dim() == 4:
             images = images.contiguous(memory_format=self.memory_format)
         if getattr(c, 'with_scaling', False) and not getattr(c, 'use_gaussian_noise', False):
@@ -229,14 +283,14 @@ class MMD_GAN:
         self._need_critic_grad = need_critic_grad
         self.aux = None
         if getattr(c, "L2_discriminator_penalty", 0) > 0:
-            self.d_images_layers = D(images, return_layers=True)
-            self.d_G_layers = D(fake, return_layers=True)
+            self.d_images_layers = D(images, return_layers=True, **real_kw)
+            self.d_G_layers = D(fake, return_layers=True, **fake_kw)
             self.d_images = self.d_images_layers['hF']
             self.d_G = self.d_G_layers['hF']
         else:
             self.d_images_layers = self.d_G_layers = None
-            self.d_images = D(images)
-            self.d_G = D(fake)
+            self.d_images = D(images, **real_kw)
+            self.d_G = D(fake, **fake_kw)
         # mmd.mmd2 inside set_loss spans the global batch in the all-gather
         # mode, and one all-gather carries the features and the scale's partials
         grp = self._loss_group()
@@ -488,18 +542,19 @@ class MMD_GAN:
         else:
             opt.step()
 
-    def d_step(self, images):
+    def d_step(self, images, labels=None):
+        labels = self._check_labels(labels)
         self.sn_D.refresh(update_u=True)
         if self.sn_G.entries:
             self.sn_G.refresh(update_u=True)
         ref = self.schedule == 'reference'
         with torch.set_grad_enabled(ref):
-            fake = self.generator(self.sample_z(self.batch_size))
+            fake, y = self._generate(self.batch_size)
         for p in self.d_vars:
             p.requires_grad_(True)
         self.d_optim.gather = GRAD_GATHER and not self.dp
         self.d_optim.zero_grad()
-        g_loss, d_loss, aux = self.set_tower_loss(images, fake, need_critic_grad=True)
+        g_loss, d_loss, aux = self.set_tower_loss(images, fake, True, labels, y)
         self._arm(self.d_optim)
         if ref:       # the generator's gradient set, computed and discarded
             torch.autograd.grad(g_loss, self.g_vars, retain_graph=True)
@@ -610,12 +665,13 @@ class MMD_GAN:
                 net._fold_cache = None
         return self.g_loss, self.d_loss, aux
 
-    def g_step(self, images):
+    def g_step(self, images, labels=None):
         # critic weights are constants of the generator update: freeze them
         # BEFORE the SN refresh so W_eff does not require grad (otherwise the
         # backward runs every critic conv's weight-gradient kernel and the SN
         # weight backward, and discards them)
         ref = self.schedule == 'reference'
+        labels = self._check_labels(labels)
         if not ref:
             for p in self.d_vars:
                 p.requires_grad_(False)
@@ -630,8 +686,8 @@ class MMD_GAN:
             # all-reduce, collectives.GradBuckets._launch)
             self.g_optim.gather = GRAD_GATHER
             self.g_optim.zero_grad()
-            fake = self.generator(self.sample_z(self.batch_size))
-            g_loss, d_loss, aux = self.set_tower_loss(images, fake, need_critic_grad=ref)
+            fake, y = self._generate(self.batch_size)
+            g_loss, d_loss, aux = self.set_tower_loss(images, fake, ref, labels, y)
             if ref:   # the critic's gradient set, computed and discarded
                 torch.autograd.grad(d_loss, self.d_vars, retain_graph=True)
             self._arm(self.g_optim)
@@ -642,18 +698,20 @@ class MMD_GAN:
                 p.requires_grad_(True)
         return self._detach_step_state()
 
-    def train_step(self, images):
-        """model.py:507-546 (lean: only the gradient set being applied)."""
+    def train_step(self, images, labels=None):
+        """model.py:507-546 (lean: only the gradient set being applied).
+        ``labels``: the batch's classes, for a conditional model only."""
         step = self.step
         self.set_counters(step)
         graphs = getattr(self, '_graphs', None)
+        kw = {} if labels is None else dict(labels=labels)
         if self.d_counter == 0:
             g_loss, d_loss, aux = (graphs.run(False, images) if graphs is not None
-                                   else self.g_step(images))
+                                   else self.g_step(images, **kw))
             self.step += 1                                   # global_step (model.py:460-463)
         else:
             g_loss, d_loss, aux = (graphs.run(True, images) if graphs is not None
-                                   else self.d_step(images))
+                                   else self.d_step(images, **kw))
         self.last = {'g_loss': g_loss.detach(), 'd_loss': d_loss.detach(), 'aux': aux}
         return g_loss, d_loss, step
 
@@ -665,6 +723,10 @@ class MMD_GAN:
                 self._graphs.close()
             self._graphs = None
             return
+        if getattr(self, 'with_labels', False):
+            raise NotImplementedError(
+                'conditional model: step graphs are not built (the label buffers and the '
+                'sample_y draw are unproven under capture)')
         if self.dp:
             raise NotImplementedError('step graphs are single-GPU (the collectives run eagerly)')
         if self.schedule != 'lean':
@@ -686,7 +748,7 @@ class MMD_GAN:
         the reference's)."""
         out, have = [], 0
         while have < n:
-            out.append(self.generator(self.sample_z(self.batch_size)))
+            out.append(self._generate(self.batch_size)[0])
             have += out[-1].shape[0]
         return torch.cat(out)[:n]
 

@@ -340,14 +340,28 @@ class Cifar10(Pipeline):
         return out
 
 
+def check_label_range(label, num_classes, source):
+    """A class label must index the conditional tables: checked on the host,
+    where it is read, so no training step reads a label back from the device."""
+    if num_classes is not None and not 0 <= label < num_classes:
+        raise ValueError('label %d outside [0, %d) in %s' % (label, num_classes, source))
+    return label
+
+
 class DataFlow(Pipeline):
     """TFRecord shards -> decoded uint8 batches on a host thread (``prefetch``
-    batches ahead) -> GPU: /255, resize, NCHW."""
+    batches ahead) -> GPU: /255, resize, NCHW.  ``with_labels``: ``next()``
+    returns (images, labels), the labels int64 [batch] from
+    ``image/class/label`` (pipeline.py:181-193), each inside [0, num_classes)."""
     regex = 'tf_records_train/train-*'
     buffer_size = 4000
+    with_labels = False
+    num_classes = None
 
-    def __init__(self, *args, workers=16, prefetch=3, seed=301, verify=False, **kwargs):
+    def __init__(self, *args, workers=16, prefetch=3, seed=301, verify=False, with_labels=False,
+                 num_classes=None, **kwargs):
         super().__init__(*args, **kwargs)
+        self.with_labels, self.num_classes = bool(with_labels), num_classes
         files = sorted(glob.glob(os.path.join(self.data_dir, self.regex)))
         if not files:
             raise FileNotFoundError('no TFRecord shards match %s'
@@ -363,14 +377,15 @@ class DataFlow(Pipeline):
         self.thread = threading.Thread(target=self._produce, daemon=True)
         self.thread.start()
 
-    def _records(self):
+    def _records(self, with_source=False):
         """Endless shuffled stream: shards in random order each pass, records
-        through a shuffle buffer of ``buffer_size``."""
+        through a shuffle buffer of ``buffer_size``.  ``with_source``: yield
+        (record, its shard's path)."""
         buf = []
         while True:
             for i in self.rng.permutation(len(self.files)):
                 for rec in read_tfrecords(self.files[i], self.verify):
-                    buf.append(rec)
+                    buf.append((rec, self.files[i]) if with_source else rec)
                     if len(buf) >= self.buffer_size:
                         j = int(self.rng.integers(len(buf)))
                         buf[j], buf[-1] = buf[-1], buf[j]
@@ -380,12 +395,17 @@ class DataFlow(Pipeline):
 
     def _produce(self):
         try:
-            recs = self._records()
+            recs = self._records(with_source=self.with_labels)
             while not self._stop.is_set():
                 batch = [next(recs) for _ in range(self.batch_size)]
                 seeds = self.rng.integers(0, 2 ** 31, size=len(batch))
-                imgs = list(self.pool.map(self._decode, batch, seeds))
-                arr = np.stack(imgs, 0)
+                if self.with_labels:
+                    pairs = list(self.pool.map(self._decode_labelled, batch, seeds))
+                    arr = (np.stack([p[0] for p in pairs], 0),
+                           np.asarray([p[1] for p in pairs], np.int64))
+                else:
+                    imgs = list(self.pool.map(self._decode, batch, seeds))
+                    arr = np.stack(imgs, 0)
                 while not self._stop.is_set():
                     try:
                         self.q.put(arr, timeout=0.1)
@@ -402,6 +422,15 @@ class DataFlow(Pipeline):
         img = decode_jpeg(ex['image/encoded'][0], self.c_dim)
         return self.preprocess_host(img, np.random.default_rng(seed))
 
+    def _decode_labelled(self, item, seed):
+        rec, source = item
+        ex = parse_example(rec)
+        if not len(ex.get('image/class/label', ())):
+            raise ValueError('record without image/class/label in %s' % source)
+        label = check_label_range(int(ex['image/class/label'][0]), self.num_classes, source)
+        img = decode_jpeg(ex['image/encoded'][0], self.c_dim)
+        return self.preprocess_host(img, np.random.default_rng(seed)), label
+
     def preprocess_host(self, img, rng):
         return img
 
@@ -409,6 +438,12 @@ class DataFlow(Pipeline):
         arr = self.q.get()
         if arr is None:
             raise RuntimeError('input pipeline failed') from self._err
+        if self.with_labels:
+            arr, labels = arr
+            return self._images(arr), torch.from_numpy(labels).to(self.device)
+        return self._images(arr)
+
+    def _images(self, arr):
         x = torch.from_numpy(arr)
         if self.device.type == 'cuda':
             x = x.pin_memory()

@@ -353,6 +353,151 @@ def bn_relu(bn, x):
     return F.relu(bn(x))
 
 
+# SMMD_COND_BN=0: the conditional batch norm + relu by torch ops
+COND_BN = os.environ.get('SMMD_COND_BN', '1') != '0'
+
+
+class CondBatchNorm2d(nn.Module):
+    """resnet/ops/cond_batchnorm.py:6-17: batch norm on the batch's own
+    statistics (no moving averages) whose scale and offset are the rows
+    ``labels`` of two [num_classes, C] tables (ones, zeros)."""
+
+    def __init__(self, num_classes, C, eps=1e-5):
+        super().__init__()
+        self.num_classes, self.C, self.eps = int(num_classes), int(C), float(eps)
+        self.scale = nn.Parameter(torch.ones(self.num_classes, self.C))
+        self.offset = nn.Parameter(torch.zeros(self.num_classes, self.C))
+
+    def forward(self, x, y):
+        return _cond_bn_torch(x, self.scale, self.offset, y, self.eps, relu=False)
+
+
+def labels_int32(y):
+    """The labels as the library reads them: int32, contiguous (a network
+    casts once per forward and hands the result to every layer)."""
+    return y if y.dtype == torch.int32 and y.is_contiguous() else y.to(torch.int32).contiguous()
+
+
+def _cond_bn_torch(x, scale, offset, y, eps, relu=True):
+    C = x.shape[1]
+    mean = x.mean((0, 2, 3), keepdim=True)
+    inv = torch.rsqrt(x.var((0, 2, 3), unbiased=False, keepdim=True) + eps)
+    z = ((x - mean) * inv) * scale.index_select(0, y).view(-1, C, 1, 1) \
+        + offset.index_select(0, y).view(-1, C, 1, 1)
+    return F.relu(z) if relu else z
+
+
+def _cond_bn_relu_fwd(bn, x, y32, save):
+    from . import _lib
+    N, C, H, W = x.shape
+    L = _lib.lib()
+    ws = _lib.workspace('cond_bn_relu', L.smmd_cond_bn_relu_workspace_bytes(N, C), x.device)
+    out = torch.empty_like(x)
+    _lib.add_bytes('smmd_cond_bn_relu_fwd', 3 * x.numel() * 4)
+    with _lib.timed('smmd_cond_bn_relu_fwd'):
+        st = L.smmd_cond_bn_relu_fwd(_lib.ptr(x), _lib.ptr(y32), N, C, H * W, bn.num_classes,
+                                     _lib.ptr(bn.scale), _lib.ptr(bn.offset), bn.eps,
+                                     _lib.ptr(out), _lib.ptr(save), _lib.ptr(ws), ws.numel(),
+                                     _lib.stream_handle(x.device))
+    _lib.check(st, 'smmd_cond_bn_relu_fwd')
+    return out
+
+
+class _CondBNReLU(torch.autograd.Function):
+    """relu(cond_batch_norm(x, y)) on the library's forward (statistics;
+    normalise + per-sample table rows + ReLU) and backward
+    (smmd_cond_bn_relu_bwd).  A second-order backward is formed from torch ops
+    on statistics recomputed from x, so it stays differentiable (_BNReLU)."""
+
+    @staticmethod
+    def forward(ctx, x, scale, offset, y32, bn):
+        save = torch.empty(3 * x.shape[1], device=x.device, dtype=torch.float32)
+        out = _cond_bn_relu_fwd(bn, x, y32, save)
+        ctx.save_for_backward(x, scale, offset, y32, save)
+        ctx.eps, ctx.num_classes = bn.eps, bn.num_classes
+        return out
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, scale, offset, y32, save = ctx.saved_tensors
+        N, C, H, W = x.shape
+        if torch.is_grad_enabled():             # create_graph: differentiable torch ops
+            mean = x.mean((0, 2, 3), keepdim=True)
+            inv = torch.rsqrt(x.var((0, 2, 3), unbiased=False, keepdim=True) + ctx.eps)
+            xh = (x - mean) * inv
+            gm = scale.index_select(0, y32).view(N, C, 1, 1)
+            z = xh * gm + offset.index_select(0, y32).view(N, C, 1, 1)
+            gz = gy * (z > 0).to(gy.dtype)
+            a, b = gz.sum((2, 3)), (gz * xh).sum((2, 3))
+            go = torch.zeros_like(offset).index_add(0, y32, a)
+            gs = torch.zeros_like(scale).index_add(0, y32, b)
+            M = float(N * H * W)
+            s1 = (gm.view(N, C) * a).sum(0).view(1, C, 1, 1)
+            s2 = (gm.view(N, C) * b).sum(0).view(1, C, 1, 1)
+            gx = inv * (gm * gz - s1 / M - xh * s2 / M)
+            return gx, gs, go, None, None
+        from . import _lib
+        gy = gy.contiguous()
+        L = _lib.lib()
+        ws = _lib.workspace('cond_bn_relu', L.smmd_cond_bn_relu_workspace_bytes(N, C), x.device)
+        gx = torch.empty_like(x)
+        gs, go = torch.empty_like(scale), torch.empty_like(offset)
+        _lib.add_bytes('smmd_cond_bn_relu_bwd', 5 * x.numel() * 4)
+        with _lib.timed('smmd_cond_bn_relu_bwd'):
+            st = L.smmd_cond_bn_relu_bwd(_lib.ptr(x), _lib.ptr(gy), _lib.ptr(y32), N, C, H * W,
+                                         ctx.num_classes, _lib.ptr(scale), _lib.ptr(offset),
+                                         _lib.ptr(save), _lib.ptr(gx), _lib.ptr(gs), _lib.ptr(go),
+                                         _lib.ptr(ws), ws.numel(), _lib.stream_handle(x.device))
+        _lib.check(st, 'smmd_cond_bn_relu_bwd')
+        return gx, gs, go, None, None
+
+
+def _cond_bn_relu_ok(bn, x, y):
+    return (x.is_cuda and y.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+            and x.is_contiguous() and (x.shape[2] * x.shape[3]) % 4 == 0
+            and x.data_ptr() % 16 == 0 and bn.scale.is_contiguous()
+            and bn.offset.is_contiguous() and bn.scale.dtype == torch.float32)
+
+
+def cond_bn_relu(bn, x, y):
+    """relu(cond_batch_norm(x, y)) (resnet/block.py:42-47 Normalize in mode
+    'cond_batchnorm', then tf.nn.relu) for a CondBatchNorm2d on an NCHW device
+    tensor and labels y [N], on the library: without a gradient (the
+    generator's forward in every critic step) smmd_cond_bn_relu_fwd, with one
+    (the generator step) the same forward and smmd_cond_bn_relu_bwd
+    (_CondBNReLU).  CPU tensors, other dtypes or layouts and HW % 4 != 0 take
+    torch ops in the same arithmetic; so does everything with SMMD_COND_BN=0."""
+    if y is None:
+        raise ValueError('conditional batch norm needs the labels')
+    if COND_BN and _cond_bn_relu_ok(bn, x, y):
+        y32 = labels_int32(y)
+        if not torch.is_grad_enabled():
+            return _cond_bn_relu_fwd(bn, x, y32, None)
+        return _CondBNReLU.apply(x, bn.scale, bn.offset, y32, bn)
+    return _cond_bn_torch(x, bn.scale, bn.offset, y, bn.eps)
+
+
+class LinearOneHot(nn.Module, _SNMixin):
+    """snops.linear_one_hot (snops.py:208-228): the rows ``y`` of a
+    [num_classes, out] matrix (random normal, std 0.01), spectrally normalised
+    as a whole (``s`` as for Linear).  A lookup is a linear layer on a one-hot
+    input: the weight is kept as Linear keeps it, [out, num_classes] (the
+    reference's Matrix transposed, u on the ``out`` side as there), so the
+    network's SpectralNormBank and FlatAdam treat it as any Linear, and the
+    lookup selects columns of the bank's effective weight."""
+
+    def __init__(self, num_classes, cout, with_sn=False, with_learnable_sn_scale=False,
+                 scale=1.0, stddev=0.01):
+        super().__init__()
+        self.num_classes = int(num_classes)
+        self.weight = nn.Parameter(torch.empty(cout, self.num_classes))
+        nn.init.normal_(self.weight, 0.0, stddev)
+        self._init_sn(with_sn, with_learnable_sn_scale, scale)
+
+    def forward(self, y):
+        return self.effective_weight().index_select(1, y).t()
+
+
 def lrelu(x, leak=0.2):
     """max(x, leak * x)  (snops.py:165-166)."""
     return F.leaky_relu(x, leak)

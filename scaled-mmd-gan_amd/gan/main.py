@@ -69,6 +69,8 @@ _FLAGS = [
     # this build: scorer features ('inception' is the reference's and is
     # unavailable offline; 'random' = seeded random features, gan/utils/featurizer.py)
     ('featurizer', 'inception', str),
+    # this build: the classes of -with_labels true (the reference fixes 1000, model.py:83)
+    ('num_classes', 1000, int),
 ]
 _DOUBLE_DASH = [('use-incomplete-cho', True, str2bool), ('incho-eta', 1e-3, float),
                 ('incho-max-steps', 1000, int)]
@@ -211,7 +213,7 @@ def make_scorer(flags, pipe, dev, size):
     else:
         ims, n = [], 0
         while n < SCORE_SIZE:
-            b = pipe.next()
+            b, _ = next_batch(pipe)
             ims.append(feat(b))
             n += b.shape[0]
         codes = torch.cat(ims)[:SCORE_SIZE].cpu().numpy()
@@ -230,7 +232,21 @@ def make_pipeline(flags, size, c_dim, dev, rank=0, world=1):
     from gan.core import pipeline as P
     args = (size, c_dim, flags.real_batch_size, flags.data_dir)
     kw = dict(device=dev, rank=rank, world=world)
-    return P.get_pipeline(flags.dataset)(*args, **kw)
+    cls = P.get_pipeline(flags.dataset)
+    if getattr(flags, 'with_labels', False):
+        # model.py:125-128: the labelled pipeline is the TFRecord one
+        if not issubclass(cls, P.DataFlow):
+            raise ValueError('-with_labels needs a TFRecord dataset with image/class/label '
+                             '(imagenet), not %r' % flags.dataset)
+        kw.update(with_labels=True, num_classes=flags.num_classes)
+    return cls(*args, **kw)
+
+
+def next_batch(pipe):
+    """(images, labels) of the pipeline's next batch; labels None without
+    -with_labels."""
+    b = pipe.next()
+    return b if isinstance(b, tuple) else (b, None)
 
 
 def main(argv=None):
@@ -287,7 +303,7 @@ def _train(flags, dev, world, rank, size, c_dim):
             scoring = scorer is not None
         try:
             while step <= flags.max_iteration:
-                _, _, step = gan.train_step(pipe.next())
+                _, _, step = gan.train_step(*next_batch(pipe))
                 if gan.d_counter == 0 and (step % 100 == 0 or step <= 10):
                     g, d = gan.check_finite()
                     if rank == 0:
