@@ -992,6 +992,36 @@ smmd_status smmd_critic_head_fwd(const float *d_real, int n_real, const float *d
                                  int kind, float *out, float *g_real, float *g_fake,
                                  float *gg_fake, smmd_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * FID scoring: the moments of gathered code rows (gan/compute_scores.py:193-197,
+ * part.mean(axis=0) and np.cov(part, rowvar=False) for part = codes[index]).
+ *
+ * smmd_code_moments: codes [n_rows, dim] row-major fp32 (any dim: rows need not
+ *   be 16-byte aligned), index [n] int64 row numbers in [0, n_rows), repeats
+ *   allowed (bootstrap), or NULL for rows 0..n-1 (then n <= n_rows); n >= 2.
+ *   mean [dim] and cov [dim, dim] in double, cov normalised by n - 1 and
+ *   exactly symmetric.  Index VALUES are not checked (they live on the
+ *   device): the caller validates them.
+ *   Arithmetic: column sums in double (per-slab partials combined in slab
+ *   order) give mean and the shift c = float(mean); S = sum_r (x_r - c)(x_r -
+ *   c)^T on the f32 matrix cores, subtraction and products in f32, a running
+ *   f32 sum over 32 consecutive rows folded into double registers;
+ *   double split-K slabs added in slice order; cov = (S - n delta delta^T) /
+ *   (n - 1), delta = mean - c in double.  Only block tiles on or above the
+ *   diagonal are computed; the mirror is written from the same values.  No
+ *   floating-point atomics: two runs give the same bits.
+ *   Workspace from smmd_code_moments_workspace_bytes (0 for an unsupported
+ *   size): shift, residual, column-sum partials and the slabs.  It holds no
+ *   counters: it needs no particular contents on entry (a zero-filled buffer
+ *   like every other workspace will do) and every byte the call writes there is
+ *   a function of the call's arguments alone.
+ * ------------------------------------------------------------------------- */
+size_t smmd_code_moments_workspace_bytes(int n, int dim);
+
+smmd_status smmd_code_moments(const float *codes, int n_rows, int dim, const int64_t *index, int n,
+                              double *mean, double *cov, void *ws, size_t ws_bytes,
+                              smmd_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -209,6 +209,8 @@ _SIGS = {
     'smmd_gp_slope_fwd': (_I, [_P, _I, _I, _I, _I, _F, _P, _P, _P, _SZ, _P]),
     'smmd_gp_slope_bwd': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
     'smmd_critic_head_fwd': (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
+    'smmd_code_moments_workspace_bytes': (_SZ, [_I, _I]),
+    'smmd_code_moments': (_I, [_P, _I, _I, _P, _I, _P, _P, _P, _SZ, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

@@ -71,6 +71,9 @@ _FLAGS = [
     ('featurizer', 'inception', str),
     # this build: the classes of -with_labels true (the reference fixes 1000, model.py:83)
     ('num_classes', 1000, int),
+    # this build: also score the FID each round (the reference always does,
+    # scorer.py:95-101; off by default here so existing runs draw and log as before)
+    ('compute_fid', False, str2bool),
 ]
 _DOUBLE_DASH = [('use-incomplete-cho', True, str2bool), ('incho-eta', 1e-3, float),
                 ('incho-max-steps', 1000, int)]
@@ -221,7 +224,7 @@ def make_scorer(flags, pipe, dev, size):
             np.save(path, codes)
         except OSError:
             pass
-    return Scorer(codes, lr_scheduler=flags.MMD_lr_scheduler), feat
+    return Scorer(codes, lr_scheduler=flags.MMD_lr_scheduler, fid=flags.compute_fid), feat
 
 
 def make_pipeline(flags, size, c_dim, dev, rank=0, world=1):

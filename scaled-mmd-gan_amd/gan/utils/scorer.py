@@ -1,7 +1,10 @@
-"""KID scoring and the 3-sample learning-rate scheduler of gan/utils/scorer.py.
+"""KID and FID scoring and the 3-sample learning-rate scheduler of
+gan/utils/scorer.py.
 
 ``Scorer.compute`` follows the reference (:65-170) from the point where the
-Inception codes exist: KID over 10 subsets of 1000 (:103-111, best-model
+Inception codes exist: with ``fid=True`` the FID over 3 bootstrap splits
+(:95-101, ahead of the KID as there: both draw from np.random), then KID over
+10 subsets of 1000 (:103-111, best-model
 callback :113-117), then the 3-sample test between the training codes X, the
 current samples Y and a sample Z from ``MMD_sdlr_past_sample`` scorings ago
 (:119-162): if p = Phi(test statistic) > 0.1 ``MMD_sdlr_num_test`` times in a
@@ -27,12 +30,14 @@ def _norm_cdf(x):
 
 class Scorer:
     def __init__(self, train_codes, lr_scheduler=True, n_subsets=10, subset_size=1000,
-                 three_sample_size=2048):
+                 three_sample_size=2048, fid=False, fid_splits=3):
         self.train_codes = np.asarray(train_codes, dtype=np.float32)
         self.lr_scheduler = lr_scheduler
         self.n_subsets = n_subsets
         self.subset_size = subset_size
         self.bs = three_sample_size
+        self.fid = fid
+        self.fid_splits = fid_splits
         self.output = []
         self.three_sample = []
         self.three_sample_chances = 0
@@ -42,6 +47,12 @@ class Scorer:
         if step % gan.config.MMD_sdlr_freq != 0:
             return None
         output = {}
+        if self.fid:
+            output['fid'] = fid = cs.fid_score(codes, self.train_codes, split_method='bootstrap',
+                                               splits=self.fid_splits)
+            timer = getattr(gan, 'timer', None)
+            if timer is not None:
+                timer(step, "FID mean (std): %f (%f)" % (fid.mean(), fid.std()))
         output['mmd2'] = mmd2s = cs.polynomial_mmd_averages(
             codes, self.train_codes, n_subsets=self.n_subsets, subset_size=self.subset_size,
             ret_var=False)
