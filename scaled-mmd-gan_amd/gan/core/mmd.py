@@ -56,6 +56,9 @@ class KernelSpec:
     _desc: object = field(default=None, compare=False, repr=False)
 
     def desc(self):
+        if len(self.params) > _lib.SMMD_MAX_TERMS:
+            raise ValueError('kernel %r has %d terms, the library takes at most SMMD_MAX_TERMS '
+                             '= %d' % (self.name, len(self.params), _lib.SMMD_MAX_TERMS))
         d = _lib.KernelDesc()
         d.kind = self.kind
         d.n_terms = len(self.params)

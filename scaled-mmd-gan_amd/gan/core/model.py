@@ -370,7 +370,7 @@ class MMD_GAN:
             return
         bs = min(self.batch_size, self.real_batch_size)
         real, fake = real[:bs], fake[:bs]
-        alpha = torch.rand(bs, 1, 1, 1, device=self.device)
+        alpha = self.sample_alpha(bs)
         x_hat_data = ((1.0 - alpha) * self.images[:bs].detach()
                       + alpha * self.G[:bs].detach()).requires_grad_(True)
         x_hat = self.discriminator(x_hat_data)                    # NO_OPS (model.py:335)

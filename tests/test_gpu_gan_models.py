@@ -1,10 +1,13 @@
-"""The GAN and WGAN-GP critic updates on the GPU against float64.
+"""The GAN, WGAN-GP and witness-penalty MMD critic updates on the GPU against
+float64.
 
 The float64 side is built here: a deep copy of the model's critic in double
 on the CPU, the same images, the same generated batch (taken from the model's
 generator and fed to both sides), the same alpha (through ``sample_alpha``),
 and the reference formulas (gan/core/gan.py:10-11, gan/core/wgan_gp.py:10-27)
-in plain torch with ``create_graph=True``.  Bounds are those of
+in plain torch with ``create_graph=True``; for ``-model mmd -gradient_penalty``
+the kernel is oracle/torch_kernels.py and the penalty model.py:327-350 written
+out.  Bounds are those of
 tests/test_gpu_model.py for batch < 64: d_loss rtol 1e-3; per tensor
 |d| <= max(2e-3 max|ref|, 5e-5 gmax) + 2e-3 |ref|; relative Frobenius error
 <= 1e-3 for tensors above the noise floor.
@@ -189,6 +192,98 @@ def test_wgan_gp_penalty_matters(dev):
                                           alpha0, 0.0)
     got_loss, got_grads = _critic_step(plain, images0)
     _compare(got_loss, got_grads, ref0_loss, ref0_grads)       # the plain step is right too
+    tols, _ = _tolerances(ref_grads)
+    far = [i for i, (g0, ref, tol) in enumerate(zip(got_grads, ref_grads, tols))
+           if ref.dim() == 4 and (np.abs(g0.numpy() - ref.numpy()) > 10 * tol).any()]
+    print('tensors where the penalty exceeds 10x the tolerance:', far)
+    assert far, 'the penalty changes no convolution weight gradient beyond the tolerance'
+
+
+# -model mmd -gradient_penalty 1 -dof_dim 16: the witness penalty (model.py:327-350).
+# A float64 sweep on the CPU (dcgan critic, width 16, 32x32, this seed, uniform
+# images) of the factor every critic parameter is multiplied by:
+#   mix_rq_1dot  the witness slopes (channel norm of d sum(witness)/d x_hat per
+#                pixel) have median 0.003 at 1, 0.11 at 5, 1.0 at 6.5, 2.1 at 7
+#                and 7.7 at 8; at 7.0, 5 % lie under 0.5 and 67 % over 1.5, and
+#                the penalty moves every convolution weight gradient by 1.4 -
+#                1.9 x the tenfold tolerance (0.4 - 0.5 x at 6.5)
+#   rbf          exp(-|.|^2 / 2) saturates before the slopes grow (median 0.026
+#                at 5, mmd2 = 1 from 6 on): the penalty value stays near 1, but
+#                at 5.0 its gradient is 3.6 - 11.8 x the tenfold tolerance of
+#                each convolution weight, against an mmd2 of 0.88
+MMD_GP_FACTOR = {'mix_rq_1dot': 7.0, 'rbf': 5.0}
+MMD_GP_KW = dict(architecture='dcgan', output_size=32, df_dim=16, gf_dim=16, dof_dim=16)
+
+
+def _mmd_reference(key, model, images, fake, alpha, kernel, gp):
+    """(d_loss, [gradient per critic parameter], slopes) of MMD_GAN.set_loss
+    in float64 on the CPU: mmd2 of the kernel matrices (mmd.py:194-220) and
+    model.py:327-350 written out -- interpolates, witness row means, gradient
+    with create_graph, safer_norm over the channel axis, mean((. - 1)^2)."""
+    if key in _REFS:
+        return _REFS[key]
+    from oracle import smmd_oracle as O
+    from oracle.torch_kernels import kernel_xy
+    D = copy.deepcopy(model.discriminator).double().cpu()
+    params = [p for p in D.parameters() if p.requires_grad]
+    x, y, a = (t.detach().double().cpu().contiguous() for t in (images, fake, alpha))
+    spec = O.kernel_spec(kernel)
+    dI, dG = D(x), D(y)
+    g_loss = O.mmd2_from_K(kernel_xy(spec, dG, dG), kernel_xy(spec, dG, dI),
+                           kernel_xy(spec, dI, dI), spec.const_diag)         # model.py:313-317
+    d_loss = -g_loss
+    slopes = None
+    if gp > 0:
+        xh = ((1.0 - a) * x + a * y).requires_grad_(True)                   # model.py:331-333
+        hx = D(xh)
+        witness = kernel_xy(spec, hx, dI).mean(1) - kernel_xy(spec, hx, dG).mean(1)
+        grad, = torch.autograd.grad(witness.sum(), xh, create_graph=True)    # model.py:339
+        slopes = torch.sqrt((grad * grad).sum(1) + 1.0e-5)                   # ops.py:203-206
+        d_loss = d_loss + gp * ((slopes - 1.0) ** 2).mean()                  # model.py:341-344
+    grads = torch.autograd.grad(d_loss, params, allow_unused=True)
+    grads = [torch.zeros_like(p) if g is None else g.detach() for g, p in zip(grads, params)]
+    _REFS[key] = (float(d_loss.detach()), grads, None if slopes is None else slopes.detach())
+    return _REFS[key]
+
+
+@pytest.mark.parametrize('cl', [False, True], ids=['nchw', 'nhwc'])
+@pytest.mark.parametrize('kernel', ['mix_rq_1dot', 'rbf'])
+def test_mmd_witness_gp_critic_step_matches_float64(dev, kernel, cl):
+    model, images, fake, alpha = _build('mmd', dev, MMD_GP_FACTOR[kernel], cl=cl, kernel=kernel,
+                                        gradient_penalty=1.0, **MMD_GP_KW)
+    assert not model.sn_D.entries                     # no SN, and no batch norm under a penalty
+    ref_loss, ref_grads, slopes = _mmd_reference(('mmd', kernel, 1.0), model, images, fake,
+                                                 alpha, kernel, 1.0)
+    print('slopes: median %.3g, under 0.5 %.2f, over 1.5 %.2f' % (
+        float(slopes.median()), float((slopes < 0.5).double().mean()),
+        float((slopes > 1.5).double().mean())))
+    if kernel == 'mix_rq_1dot':       # the penalty is not trivially ~1: slopes around and above 1
+        assert 1.0 < float(slopes.median()) < 4.0
+    got_loss, got_grads = _critic_step(model, images)
+    _compare(got_loss, got_grads, ref_loss, ref_grads)
+    assert model.optim_name == 'kernel_loss_(gp 1.0)'
+
+
+@pytest.mark.parametrize('kernel', ['mix_rq_1dot', 'rbf'])
+def test_mmd_witness_gp_penalty_matters(dev, kernel):
+    """A dropped or mis-signed second-order term cannot pass: the
+    gradient_penalty=0 step meets every bound against its own float64
+    reference and differs from the penalised reference by more than 10x the
+    tolerance in a convolution weight (MMD_GP_FACTOR's sweep)."""
+    kw = dict(MMD_GP_KW, kernel=kernel)
+    model, images, fake, alpha = _build('mmd', dev, MMD_GP_FACTOR[kernel], gradient_penalty=1.0,
+                                        **kw)
+    _, ref_grads, _ = _mmd_reference(('mmd', kernel, 1.0), model, images, fake, alpha, kernel,
+                                     1.0)
+    plain, images0, fake0, alpha0 = _build('mmd', dev, MMD_GP_FACTOR[kernel],
+                                           gradient_penalty=0.0, **kw)
+    # the dcgan generator's transposed convolutions do not repeat bit for bit
+    assert torch.equal(images0, images) and torch.allclose(fake0, fake, rtol=0, atol=1e-5)
+    ref0_loss, ref0_grads, _ = _mmd_reference(('mmd', kernel, 0.0), plain, images0, fake0,
+                                              alpha0, kernel, 0.0)
+    got_loss, got_grads = _critic_step(plain, images0)
+    _compare(got_loss, got_grads, ref0_loss, ref0_grads)
+    assert plain.optim_name == 'kernel_loss'
     tols, _ = _tolerances(ref_grads)
     far = [i for i, (g0, ref, tol) in enumerate(zip(got_grads, ref_grads, tols))
            if ref.dim() == 4 and (np.abs(g0.numpy() - ref.numpy()) > 10 * tol).any()]
