@@ -945,6 +945,63 @@ smmd_status smmd_conv1x1_wgrad_acc(const float *gy, const float *x, float *gw, i
                                    smmd_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * The 5x5 stride-2 convolutions of the DCGAN critics (architecture.py:323-343,
+ * snops.conv2d) on the f32 MFMA, fp32 NCHW (csrc/smmd_conv5s2.hip): direct
+ * implicit GEMMs over (channel, tap) whose pixel dimension is the flattened
+ * (n, row, column).  x [n, cin, h, w], wgt [cout, cin, 5, 5], y [n, cout, ho,
+ * wo]; the caller states ho, wo and the top / left padding pt, pl (0..4): taps
+ * outside [0, h) x [0, w) read as zero, so a pre-padded input (pt = pl = 0)
+ * and a symmetric padding are the same call.  Needs cin, cout % 64 == 0, every
+ * tensor under 2^29 floats and wo up to about 100 (the LDS stage of a tile's
+ * receptive field); smmd_conv5s2_supported(n, cin, cout, h, w, pt, pl) says so
+ * for ho = (h + 2 pt - 5) / 2 + 1, wo likewise.  wgt, wt, gw and the
+ * workspaces 16-byte aligned.  Deterministic: fixed-order sums, no atomics.
+ *
+ * smmd_conv5s2: y = conv(x, wgt) + bias (may be NULL).  With few output tiles
+ *   the input channels are split over workgroups whose partial outputs
+ *   (smmd_conv5s2_workspace_bytes; 0 = no split) are added in slice order.
+ * smmd_conv5s2_filter: wt = the phase-sorted transpose of wgt the input
+ *   gradient reads, [phase][cin][cout][taps] (smmd_conv5s2_filter_bytes).
+ * smmd_conv5s2_dx: gx [n, cin, h, w] = the input gradient at gy, every element
+ *   written (zero where no output touches it); one output parity phase per
+ *   workgroup (3x3, 3x2, 2x3, 2x2 taps).  Workspace as the forward.
+ * smmd_conv5s2_wgrad: gw [cout, cin, 5, 5] = sum over n, oh, ow of gy x; the
+ *   pixels are split over workgroups by output rows, the partials
+ *   (smmd_conv5s2_wgrad_workspace_bytes) added in slice order.  _acc: gw += dW.
+ * ------------------------------------------------------------------------- */
+int smmd_conv5s2_supported(int n, int cin, int cout, int h, int w, int pt, int pl);
+
+size_t smmd_conv5s2_workspace_bytes(int n, int cin, int cout, int h, int w, int ho, int wo,
+                                    int pt, int pl);
+
+smmd_status smmd_conv5s2(const float *x, const float *wgt, const float *bias, float *y, int n,
+                         int cin, int cout, int h, int w, int ho, int wo, int pt, int pl,
+                         void *ws, size_t ws_bytes, smmd_stream_t stream);
+
+size_t smmd_conv5s2_filter_bytes(int cout, int cin);
+
+smmd_status smmd_conv5s2_filter(const float *wgt, int cout, int cin, float *wt, size_t wt_bytes,
+                                smmd_stream_t stream);
+
+size_t smmd_conv5s2_dx_workspace_bytes(int n, int cin, int cout, int h, int w, int ho, int wo,
+                                       int pt, int pl);
+
+smmd_status smmd_conv5s2_dx(const float *gy, const float *wt, float *gx, int n, int cin, int cout,
+                            int h, int w, int ho, int wo, int pt, int pl, void *ws,
+                            size_t ws_bytes, smmd_stream_t stream);
+
+size_t smmd_conv5s2_wgrad_workspace_bytes(int n, int cin, int cout, int h, int w, int ho, int wo,
+                                          int pt, int pl);
+
+smmd_status smmd_conv5s2_wgrad(const float *gy, const float *x, float *gw, int n, int cin,
+                               int cout, int h, int w, int ho, int wo, int pt, int pl, void *ws,
+                               size_t ws_bytes, smmd_stream_t stream);
+
+smmd_status smmd_conv5s2_wgrad_acc(const float *gy, const float *x, float *gw, int n, int cin,
+                                   int cout, int h, int w, int ho, int wo, int pt, int pl,
+                                   void *ws, size_t ws_bytes, smmd_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * The loss side of the GAN and WGAN-GP baselines (gan/core/gan.py,
  * gan/core/wgan_gp.py).  fp32, one launch each, fixed-order reductions (no
  * float atomics: two runs give the same bits).

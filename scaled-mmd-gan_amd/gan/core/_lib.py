@@ -149,6 +149,16 @@ _SIGS = {
     'smmd_conv1x1_wgrad_workspace_bytes': (_SZ, [_I, _I, _I, _I]),
     'smmd_conv1x1_wgrad': (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _SZ, _P]),
     'smmd_conv1x1_wgrad_acc': (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _SZ, _P]),
+    'smmd_conv5s2_supported': (_I, [_I] * 7),
+    'smmd_conv5s2_workspace_bytes': (_SZ, [_I] * 9),
+    'smmd_conv5s2': (_I, [_P, _P, _P, _P] + [_I] * 9 + [_P, _SZ, _P]),
+    'smmd_conv5s2_filter_bytes': (_SZ, [_I, _I]),
+    'smmd_conv5s2_filter': (_I, [_P, _I, _I, _P, _SZ, _P]),
+    'smmd_conv5s2_dx_workspace_bytes': (_SZ, [_I] * 9),
+    'smmd_conv5s2_dx': (_I, [_P, _P, _P] + [_I] * 9 + [_P, _SZ, _P]),
+    'smmd_conv5s2_wgrad_workspace_bytes': (_SZ, [_I] * 9),
+    'smmd_conv5s2_wgrad': (_I, [_P, _P, _P] + [_I] * 9 + [_P, _SZ, _P]),
+    'smmd_conv5s2_wgrad_acc': (_I, [_P, _P, _P] + [_I] * 9 + [_P, _SZ, _P]),
     'smmd_channel_sum_workspace_bytes': (_SZ, [_I, _I]),
     'smmd_channel_sum': (_I, [_P, _I, _I, _I, _P, _P, _SZ, _P]),
     'smmd_conv3x3_thin': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),

@@ -790,6 +790,137 @@ def _c1_wgrad(gy, x, into=None):
     return gw
 
 
+# ---------------------------------------------------------------------------
+# 5x5 stride-2 convolutions (the DCGAN critics' layers, snops.Conv2d's default)
+# on the library's direct implicit-GEMM kernels (smmd_conv5s2*,
+# csrc/smmd_conv5s2.hip; SMMD_CONV5=0: MIOpen for them).  The padding is the
+# caller's: (0, 0) on the pre-padded input of an even-sized image, (2, 2) on an
+# odd-sized one; taps outside the image read as zero in the kernels.
+# ---------------------------------------------------------------------------
+CONV5 = os.environ.get('SMMD_CONV5', '1') != '0'
+# SMMD_CONV5_ALL=1: every shape the kernels tile, not only the measured ones
+# below (the A/B tool and the kernels' tests)
+CONV5_ALL = os.environ.get('SMMD_CONV5_ALL', '0') == '1'
+# (direction, ci, co, H, W) at batch >= 64 where the library beat MIOpen by
+# more than the run-to-run spread (tools/conv5_ab.py, profiles/conv5/): the
+# other wide DCGAN5 layers and directions stay on MIOpen until they do
+_K5_FASTER = {('dx', 128, 256, 19, 19)}
+
+
+def _is_k5s2(x, w, stride, padding, direction='fwd'):
+    """conv(x, w [co, ci, 5, 5], stride 2, padding (pt, pl)) -- direction
+    'fwd', 'dx' or 'wgrad' of it -- on smmd_conv5s2*: NCHW fp32 contiguous
+    device tensors, ci and co % 64 == 0 (the 3-channel first layer stays on
+    MIOpen), and a shape measured faster there unless CONV5_ALL."""
+    if not (CONV5 and w.dim() == 4 and tuple(w.shape[2:]) == (5, 5) and x.dim() == 4
+            and x.is_cuda and x.dtype == torch.float32 and w.dtype == torch.float32
+            and x.is_contiguous() and w.is_contiguous() and w.data_ptr() % 16 == 0
+            and x.shape[1] == w.shape[1]):
+        return False
+    s = tuple(stride) if isinstance(stride, (list, tuple)) else (stride, stride)
+    p = tuple(padding) if isinstance(padding, (list, tuple)) else (padding, padding)
+    if s != (2, 2):
+        return False
+    from . import _lib
+    N, ci, H, W = x.shape
+    if not _lib.lib().smmd_conv5s2_supported(N, ci, w.shape[0], H, W, int(p[0]), int(p[1])):
+        return False
+    return CONV5_ALL or (N >= 64 and (direction, ci, w.shape[0], H, W) in _K5_FASTER)
+
+
+def _k5s2_dims(xshape, co, padding):
+    """(N, ci, co, H, W, Ho, Wo, pt, pl): the kernels' shape arguments."""
+    p = tuple(padding) if isinstance(padding, (list, tuple)) else (padding, padding)
+    N, ci, H, W = xshape
+    pt, pl = int(p[0]), int(p[1])
+    return (N, ci, co, H, W, (H + 2 * pt - 5) // 2 + 1, (W + 2 * pl - 5) // 2 + 1, pt, pl)
+
+
+def _k5s2_conv(x, w, b, padding):
+    """conv2d(x, w, b, stride 2, padding) on smmd_conv5s2."""
+    from . import _lib
+    if b is not None:
+        b = b.contiguous()
+    _lib.require_cuda(x, w, b)
+    d = _k5s2_dims(x.shape, w.shape[0], padding)
+    N, ci, co, H, W, Ho, Wo = d[:7]
+    L = _lib.lib()
+    y = torch.empty((N, co, Ho, Wo), dtype=x.dtype, device=x.device)
+    nb = L.smmd_conv5s2_workspace_bytes(*d)
+    ws = _lib.workspace('conv5s2', nb, x.device) if nb else None
+    _lib.add_bytes('smmd_conv5s2', (x.numel() + y.numel() + w.numel()) * 4)
+    _lib.add_flops('smmd_conv5s2', 2 * 25 * N * Ho * Wo * ci * co)
+    with _lib.timed('smmd_conv5s2'):
+        st = L.smmd_conv5s2(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(y), *d, _lib.ptr(ws),
+                            nb, _lib.stream_handle(x.device))
+    _lib.check(st, 'smmd_conv5s2')
+    return y
+
+
+def _k5s2_filter(w):
+    """The phase-sorted transpose of w the input gradient reads, cached per
+    weight version like the Winograd filter transforms."""
+    from . import _lib
+    key = (id(w), 'k5t')
+    u, store = _filter_cache_get(key, w)
+    if u is not None:
+        return u
+    L = _lib.lib()
+    co, ci = w.shape[0], w.shape[1]
+    u = torch.empty(L.smmd_conv5s2_filter_bytes(co, ci) // 4, dtype=w.dtype, device=w.device)
+    with _lib.timed('smmd_conv5s2_filter'):
+        st = L.smmd_conv5s2_filter(_lib.ptr(materialize(w)), co, ci, _lib.ptr(u), u.numel() * 4,
+                                   _lib.stream_handle(w.device))
+    _lib.check(st, 'smmd_conv5s2_filter')
+    if store:
+        _filter_cache_put(key, w, u)
+    return u
+
+
+def _k5s2_dx(gy, w, xshape, padding):
+    """The input gradient [xshape] of conv(., w, stride 2, padding) at gy on
+    smmd_conv5s2_dx (every element written: no memset)."""
+    from . import _lib
+    _lib.require_cuda(gy, w)
+    d = _k5s2_dims(xshape, w.shape[0], padding)
+    N, ci, co, H, W, Ho, Wo = d[:7]
+    assert tuple(gy.shape) == (N, co, Ho, Wo) and gy.is_contiguous()
+    L = _lib.lib()
+    u = _k5s2_filter(w)
+    gx = torch.empty((N, ci, H, W), dtype=gy.dtype, device=gy.device)
+    nb = L.smmd_conv5s2_dx_workspace_bytes(*d)
+    ws = _lib.workspace('conv5s2_dx', nb, gy.device) if nb else None
+    _lib.add_bytes('smmd_conv5s2_dx', (gy.numel() + gx.numel() + w.numel()) * 4)
+    _lib.add_flops('smmd_conv5s2_dx', 2 * 25 * N * Ho * Wo * ci * co)
+    with _lib.timed('smmd_conv5s2_dx'):
+        st = L.smmd_conv5s2_dx(_lib.ptr(gy), _lib.ptr(u), _lib.ptr(gx), *d, _lib.ptr(ws), nb,
+                               _lib.stream_handle(gy.device))
+    _lib.check(st, 'smmd_conv5s2_dx')
+    return gx
+
+
+def _k5s2_wgrad(gy, x, padding, into=None):
+    """smmd_conv5s2_wgrad: gw [co, ci, 5, 5] of conv(x, ., stride 2, padding) at
+    gy (into: added to it)."""
+    from . import _lib
+    _lib.require_cuda(gy, x)
+    d = _k5s2_dims(x.shape, gy.shape[1], padding)
+    N, ci, co, H, W, Ho, Wo = d[:7]
+    assert tuple(gy.shape) == (N, co, Ho, Wo) and gy.is_contiguous()
+    L = _lib.lib()
+    nb = L.smmd_conv5s2_wgrad_workspace_bytes(*d)
+    ws = _lib.workspace('conv5s2_wgrad', nb, x.device) if nb else None
+    gw, acc = _gw_out(into, (co, ci, 5, 5), x)
+    _lib.add_bytes('smmd_conv5s2_wgrad', (x.numel() + gy.numel() + gw.numel()) * 4)
+    _lib.add_flops('smmd_conv5s2_wgrad', 2 * 25 * N * Ho * Wo * ci * co)
+    with _lib.timed('smmd_conv5s2_wgrad'):
+        st = getattr(L, 'smmd_conv5s2_wgrad' + acc)(
+            _lib.ptr(gy), _lib.ptr(x), _lib.ptr(gw), *d, _lib.ptr(ws), nb,
+            _lib.stream_handle(x.device))
+    _lib.check(st, 'smmd_conv5s2_wgrad')
+    return gw
+
+
 def _is_thin(x, w, stride, padding):
     return thin_applicable(x, w.shape[1], w.shape[0], w.shape[2], stride, padding) \
         and w.shape[2] == w.shape[3]
@@ -819,6 +950,8 @@ def _fwd(x, w, b, stride, padding, ymask=None, into=None):
         y = _c1_fwd(x, w, b)
         if y is not None:
             return y
+    if _is_k5s2(x, w, stride, padding):
+        return _k5s2_conv(x, materialize(w), b, padding)
     return F.conv2d(x, materialize(w), b, stride, padding)
 
 
@@ -868,6 +1001,22 @@ def _bwd_core(gy, x, w, stride, padding, mask, xmask, into=None):
         # an output the library did not tile comes from aten ALONE: a gw the
         # *_wgrad_acc kernel already added into `into` must not be formed twice
         need_x, need_w = mask[0] and gx is None, mask[1] and gw is None
+        if need_x or need_w:
+            ax, aw, _ = _aten.convolution_backward(gy, x, materialize(w), None, stride, padding,
+                                                   [1, 1], False, [0, 0], 1,
+                                                   [need_x, need_w, False])
+            gx = ax if need_x else gx
+            gw = aw if need_w else gw
+        return gx, gw, False
+    k5 = gy.is_contiguous() and gy.dtype == torch.float32
+    k5x = k5 and mask[0] and _is_k5s2(x, w, stride, padding, 'dx')
+    k5w = k5 and mask[1] and _is_k5s2(x, w, stride, padding, 'wgrad')
+    if k5x or k5w:
+        gx = _k5s2_dx(gy, w, x.shape, padding) if k5x else None
+        gw = _k5s2_wgrad(gy, x, padding, into) if k5w else None
+        # the other output from aten ALONE (the 1x1 branch's rule: a gw the
+        # *_wgrad_acc kernel added into `into` must not be formed twice)
+        need_x, need_w = mask[0] and not k5x, mask[1] and not k5w
         if need_x or need_w:
             ax, aw, _ = _aten.convolution_backward(gy, x, materialize(w), None, stride, padding,
                                                    [1, 1], False, [0, 0], 1,
