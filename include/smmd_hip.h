@@ -124,6 +124,48 @@ smmd_status smmd_mmd2_combine(const smmd_kernel_desc *desc, const float *sums,
                               smmd_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Variance-normalised MMD objective (additive to ABI 17).
+ * Replaces mmd.mmd2_and_ratio(mmd._<kind>_kernel(X, Y), biased, min_var_est)
+ * (gan/core/mmd.py:223-293) and TF's autodiff of it; no N x N array is written.
+ * The reference's values term for term: its "unbiased" mmd2 keeps the diagonal
+ * sums in the numerators (mmd.py:274-276), and a constant diagonal is
+ * subtracted from matrices that hold the computed one (:241-257).
+ *
+ * X, Y [m, d] fp32 row-major (the reference assumes equal sizes; m >= 2).
+ * out[8] (device, fp32): [0] mmd2  [1] ratio = mmd2 / sqrt(max(var_est,
+ *   min_var_est))  [2] var_est  [3] 1 when the variance was clamped, else 0
+ *   [4] the clamped variance  [5..7] zero.
+ * grad_mmd2_x/_y, grad_var_x/_y [m, d] (device; all NULL or all set): the unit
+ *   gradients d mmd2 / dX, dY and d var_est / dX, dY.
+ * ws: zero-filled at allocation, at least smmd_mmd2_ratio_workspace_bytes();
+ *   zero-filled again when the call has run.
+ * d <= 8: lane-per-row sweeps on a row-tile x column-chunk grid; d > 8: 64 x 64
+ * pair tiles on the f32 MFMA.  Sums across chunks and the estimator are double
+ * in a fixed order: two calls give equal bits.
+ *
+ * smmd_mmd2_ratio_bwd, one launch:
+ *   dZ = (g_mmd2 + g_ratio / sqrt(v)) Gm
+ *      + (g_var - g_ratio mmd2 v^(-3/2) [var_est > min_var_est] / 2) Gv
+ * with v the clamped variance, Gm / Gv the unit gradients, and the upstream
+ * gradients device scalars (NULL: 0).
+ * ------------------------------------------------------------------------- */
+size_t smmd_mmd2_ratio_workspace_bytes(int m, int d);
+
+smmd_status smmd_mmd2_ratio_fwd(const smmd_kernel_desc *desc,
+                                const float *X, const float *Y, int m, int d,
+                                int biased, double min_var_est, float *out,
+                                float *grad_mmd2_x, float *grad_mmd2_y,
+                                float *grad_var_x, float *grad_var_y,
+                                void *ws, size_t ws_bytes, smmd_stream_t stream);
+
+smmd_status smmd_mmd2_ratio_bwd(const float *out, const float *g_mmd2,
+                                const float *g_ratio, const float *g_var,
+                                const float *grad_mmd2_x, const float *grad_mmd2_y,
+                                const float *grad_var_x, const float *grad_var_y,
+                                int m, int d, float *dX, float *dY,
+                                smmd_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Witness function of the gradient penalty (gan/core/model.py:336-339):
  *   w_i = mean_j K(H_i, R_j) - mean_j K(H_i, F_j)   (K_XY_only=True kernels)
  * out_w [b] (may be NULL), out_dH [b, d] = d(sum_i w_i)/dH (may be NULL).

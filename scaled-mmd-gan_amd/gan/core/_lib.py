@@ -92,6 +92,10 @@ _SIGS = {
     'smmd_mmd2_fwd': (_I, [ctypes.POINTER(KernelDesc), _P, _I, _P, _I, _I, _I, _I, _I, _I, _I,
                            _P, _P, _P, _P, _P, _SZ, _P]),
     'smmd_mmd2_combine': (_I, [ctypes.POINTER(KernelDesc), _P, _I, _I, _I, _P, _P]),
+    'smmd_mmd2_ratio_workspace_bytes': (_SZ, [_I, _I]),
+    'smmd_mmd2_ratio_fwd': (_I, [ctypes.POINTER(KernelDesc), _P, _P, _I, _I, _I, ctypes.c_double,
+                                 _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    'smmd_mmd2_ratio_bwd': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P]),
     'smmd_witness_fwd': (_I, [ctypes.POINTER(KernelDesc), _P, _I, _P, _I, _P, _I, _I, _P, _P, _P]),
     'smmd_witness_bwd': (_I, [ctypes.POINTER(KernelDesc), _P, _I, _P, _I, _P, _I, _I, _P, _P, _P,
                               _P, _P]),

@@ -680,6 +680,129 @@ def _mmd2(K_XX, K_XY, K_YY, const_diagonal=False, biased=False):
 
 
 # ---------------------------------------------------------------------------
+# variance-normalised objective (gan/core/mmd.py:223-293)
+# ---------------------------------------------------------------------------
+def _sq_sum(t):
+    return (t * t).sum()
+
+
+def _mmd2_and_variance(K_XX, K_XY, K_YY, const_diagonal=False, biased=False):
+    """gan/core/mmd.py:236-293 on explicit matrices (any dtype and device),
+    term for term.  Two properties of the reference are kept because drop-in
+    means its values: the "unbiased" mmd2 adds the diagonal sums back into
+    the numerators (:274-276), so it differs from ``_mmd2``; and a constant
+    diagonal is subtracted from matrices that hold the computed diagonal."""
+    m = float(K_XX.shape[0])          # assumes X, Y are the same shape
+    if const_diagonal is not False:
+        c = float(const_diagonal)
+        diag_X = diag_Y = c
+        sum_diag_X = sum_diag_Y = m * c
+        sum_diag2_X = sum_diag2_Y = m * c ** 2
+    else:
+        diag_X, diag_Y = torch.diagonal(K_XX), torch.diagonal(K_YY)
+        sum_diag_X, sum_diag_Y = diag_X.sum(), diag_Y.sum()
+        sum_diag2_X, sum_diag2_Y = _sq_sum(diag_X), _sq_sum(diag_Y)
+    Kt_XX_sums = K_XX.sum(1) - diag_X
+    Kt_YY_sums = K_YY.sum(1) - diag_Y
+    K_XY_sums_0 = K_XY.sum(0)
+    K_XY_sums_1 = K_XY.sum(1)
+    Kt_XX_sum, Kt_YY_sum, K_XY_sum = Kt_XX_sums.sum(), Kt_YY_sums.sum(), K_XY_sums_0.sum()
+    Kt_XX_2_sum = _sq_sum(K_XX) - sum_diag2_X
+    Kt_YY_2_sum = _sq_sum(K_YY) - sum_diag2_Y
+    K_XY_2_sum = _sq_sum(K_XY)
+    den = m * m if biased else m * (m - 1)
+    mmd2 = ((Kt_XX_sum + sum_diag_X) / den + (Kt_YY_sum + sum_diag_Y) / den
+            - 2 * K_XY_sum / (m * m))
+    var_est = (
+        2 / (m ** 2 * (m - 1) ** 2) * (
+            2 * _sq_sum(Kt_XX_sums) - Kt_XX_2_sum + 2 * _sq_sum(Kt_YY_sums) - Kt_YY_2_sum)
+        - (4 * m - 6) / (m ** 3 * (m - 1) ** 3) * (Kt_XX_sum ** 2 + Kt_YY_sum ** 2)
+        + 4 * (m - 2) / (m ** 3 * (m - 1) ** 2) * (_sq_sum(K_XY_sums_1) + _sq_sum(K_XY_sums_0))
+        - 4 * (m - 3) / (m ** 3 * (m - 1) ** 2) * K_XY_2_sum
+        - (8 * m - 12) / (m ** 5 * (m - 1)) * K_XY_sum ** 2
+        + 8 / (m ** 3 * (m - 1)) * (
+            1 / m * (Kt_XX_sum + Kt_YY_sum) * K_XY_sum
+            - (Kt_XX_sums * K_XY_sums_1).sum() - (Kt_YY_sums * K_XY_sums_0).sum()))
+    return mmd2, var_est
+
+
+def _mmd2_and_ratio(K_XX, K_XY, K_YY, const_diagonal=False, biased=False, min_var_est=_eps):
+    """gan/core/mmd.py:228-233."""
+    mmd2, var_est = _mmd2_and_variance(K_XX, K_XY, K_YY, const_diagonal=const_diagonal,
+                                       biased=biased)
+    ratio = mmd2 / torch.sqrt(torch.clamp(var_est, min=min_var_est))
+    return mmd2, ratio, var_est
+
+
+class _MMD2Ratio(torch.autograd.Function):
+    """(mmd2, ratio, var_est) of one smmd_mmd2_ratio_fwd call, which also
+    leaves the unit gradients d mmd2 / dZ and d var_est / dZ; the backward is
+    one smmd_mmd2_ratio_bwd launch combining them."""
+
+    @staticmethod
+    def forward(ctx, X, Y, spec, biased, min_var_est):
+        X = _features(X)
+        Y = _features(Y)
+        if X.shape != Y.shape:
+            raise ValueError('mmd2_and_ratio needs X and Y of one shape (got %s and %s)'
+                             % (tuple(X.shape), tuple(Y.shape)))
+        dev = X.device
+        L = _lib.lib()
+        m, d = X.shape
+        need_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        out = torch.empty(8, device=dev, dtype=torch.float32)
+        g = [torch.empty((m, d), device=dev, dtype=torch.float32) if need_grad else None
+             for _ in range(4)]
+        ws = _lib.workspace('mmd2_ratio', L.smmd_mmd2_ratio_workspace_bytes(m, d), dev)
+        with _lib.timed('smmd_mmd2_ratio_fwd'):
+            st = L.smmd_mmd2_ratio_fwd(spec.desc(), _lib.ptr(X), _lib.ptr(Y), m, d,
+                                       1 if biased else 0, float(min_var_est), _lib.ptr(out),
+                                       *[_lib.ptr(t) for t in g], _lib.ptr(ws), ws.numel(),
+                                       _lib.stream_handle(dev))
+        _lib.check(st, 'smmd_mmd2_ratio_fwd')
+        ctx.save_for_backward(out, *g)
+        ctx.set_materialize_grads(False)
+        return out[0].view(()), out[1].view(()), out[2].view(())
+
+    @staticmethod
+    def backward(ctx, g_mmd2, g_ratio, g_var):
+        out, gmx, gmy, gvx, gvy = ctx.saved_tensors
+        if gmx is None:
+            return None, None, None, None, None
+        ups = [None if t is None else t.reshape(1).contiguous().to(torch.float32)
+               for t in (g_mmd2, g_ratio, g_var)]
+        dX, dY = torch.empty_like(gmx), torch.empty_like(gmy)
+        with _lib.timed('smmd_mmd2_ratio_bwd'):
+            st = _lib.lib().smmd_mmd2_ratio_bwd(
+                _lib.ptr(out), *[_lib.ptr(t) for t in ups], _lib.ptr(gmx), _lib.ptr(gmy),
+                _lib.ptr(gvx), _lib.ptr(gvy), gmx.shape[0], gmx.shape[1], _lib.ptr(dX),
+                _lib.ptr(dY), _lib.stream_handle(out.device))
+        _lib.check(st, 'smmd_mmd2_ratio_bwd')
+        return dX, dY, None, None, None
+
+
+def mmd2_and_ratio(K, biased=False, min_var_est=_eps):
+    """gan/core/mmd.py:223-225: (mmd2, ratio, var_est), 0-dim and
+    differentiable, ratio = mmd2 / sqrt(max(var_est, min_var_est)).
+
+    The values are the reference's (see ``_mmd2_and_variance``: its mmd2 is
+    not ``mmd2()``'s unbiased estimator).  A KernelMatrices argument takes the
+    fused launch, which writes no N x N matrix; SMMD_RATIO_FUSED=0 materialises
+    the matrices and reduces them with torch ops, as an explicit 4-tuple is.
+    The estimator spans one process's batch: inside a data-parallel
+    ``loss_group`` it is not implemented."""
+    if isinstance(K, KernelMatrices):
+        if current_loss_group() is not None:
+            raise NotImplementedError(
+                'mmd2_and_ratio in the all-gather data-parallel mode (loss_group): the '
+                'global-batch variance is not implemented')
+        if _env_first('SMMD_RATIO_FUSED') != '0':
+            return _MMD2Ratio.apply(K.X, K.Y, K.spec, bool(biased), float(min_var_est))
+    K_XX, K_XY, K_YY, const_diagonal = K
+    return _mmd2_and_ratio(K_XX, K_XY, K_YY, const_diagonal, biased, min_var_est)
+
+
+# ---------------------------------------------------------------------------
 # witness function of the gradient penalty (gan/core/model.py:336-339)
 # ---------------------------------------------------------------------------
 class _WitnessGrad(torch.autograd.Function):
