@@ -1092,6 +1092,48 @@ smmd_status smmd_critic_head_fwd(const float *d_real, int n_real, const float *d
                                  float *gg_fake, smmd_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * The loss side of the Cramer GAN (gan/core/cramer.py).  Rows of G, G2, X
+ * [b, d] (and H [bs, d]) are the critic's outputs on a generated batch, a
+ * second generated batch, the real batch (and the interpolates); n(v) =
+ * sqrt(sum(v^2) + eps) over a row (ops.py:203-206), eps >= 0.  fp32 in and
+ * out, each element formed in double and rounded once; one launch each;
+ * fixed-order reductions (no float atomics: two runs give the same bits).
+ *
+ * smmd_cramer_head_fwd: with g, g2, x the rows of sample i,
+ *   variant 0 (cramer, cramer.py:85-88):
+ *     out[1] = g_loss = mean_i[-n(g - g2) + n(g - x) + n(g2 - x)]
+ *     out[0] = d_base = mean_i[-n(x - g) + n(x) + n(g2 - g) - n(g2)]
+ *   variant 1 (reddit_cramer, cramer.py:90-92):
+ *     out[1] = g_loss = mean_i[(n(x - g) - n(x)) - (n(g - g2) - n(g))]
+ *     out[0] = d_base = -g_loss.
+ *   The same launch writes the row gradients [b, d]: want bit 0 those of
+ *   d_base (dD_dG, dD_dG2, dD_dX), bit 1 those of g_loss (dGl_*); a set that is
+ *   not wanted takes NULL.  Workspace from smmd_cramer_head_workspace_bytes,
+ *   zero at first use (the arrival ticket); the call leaves it at rest.
+ * smmd_cramer_seed_fwd: U [bs, d] = (h - g) / n(h - g) - h / n(h), the gradient
+ *   of sum_i(n(h - g) - n(h)) with respect to H: the grad_outputs of
+ *   cramer.py:96 (to_penalize of :88 / :92).  norms [bs, 2] in DOUBLE:
+ *   n(h - g), n(h) per row.  G is G's first bs rows.
+ * smmd_cramer_seed_bwd: for an upstream W [bs, d], with a = h - g and
+ *   P_v w = w / n(v) - v (v.w) / n(v)^3 (evaluated as (w n^2 - v (v.w)) / n^3):
+ *   gH = P_a w - P_h w, gG = -P_a w: what TF's autodiff sends back through the
+ *   seed when the penalty is differentiated.  norms: smmd_cramer_seed_fwd's.
+ * ------------------------------------------------------------------------- */
+size_t smmd_cramer_head_workspace_bytes(int b, int d);
+
+smmd_status smmd_cramer_head_fwd(const float *G, const float *G2, const float *X, int b, int d,
+                                 int variant, float eps, int want, float *out, float *dD_dG,
+                                 float *dD_dG2, float *dD_dX, float *dGl_dG, float *dGl_dG2,
+                                 float *dGl_dX, void *ws, size_t ws_bytes, smmd_stream_t stream);
+
+smmd_status smmd_cramer_seed_fwd(const float *H, const float *G, int bs, int d, float eps, float *U,
+                                 double *norms, smmd_stream_t stream);
+
+smmd_status smmd_cramer_seed_bwd(const float *H, const float *G, const double *norms,
+                                 const float *W, int bs, int d, float *gH, float *gG,
+                                 smmd_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * FID scoring: the moments of gathered code rows (gan/compute_scores.py:193-197,
  * part.mean(axis=0) and np.cov(part, rowvar=False) for part = codes[index]).
  *

@@ -10,6 +10,9 @@
 * ``gp_interpolate`` / ``slope_penalty`` / ``critic_head_loss``: the loss side
   of the GAN and WGAN-GP baselines (gan/core/gan.py:10-11,
   gan/core/wgan_gp.py:10-25), one HIP launch forward and one backward each.
+* ``cramer_head_loss`` / ``cramer_seed``: the loss side of the Cramer GAN
+  (gan/core/cramer.py:81-96): the energy-distance head with its row gradients
+  in one launch, the penalty's seed and the seed's backward in one each.
 """
 from __future__ import annotations
 
@@ -464,3 +467,153 @@ def critic_head_loss(d_real, d_fake, kind):
         sp = torch.nn.functional.softplus
         return sp(-d_real).mean() + sp(d_fake).mean(), sp(-d_fake).mean()
     return _CriticHead.apply(d_real, d_fake, kind)
+
+
+# ---------------------------------------------------------------------------
+# the loss side of the Cramer GAN (csrc/smmd_cramer.hip): the energy-distance
+# head with the row gradients of both losses in one launch, and the penalty's
+# seed with its own backward.  SMMD_CRAMER_FUSED=0 routes them through plain
+# tensor ops written with safer_norm (A/B); CPU or non-fp32 tensors take that
+# path too, so the model also builds and steps without a GPU.
+# ---------------------------------------------------------------------------
+CRAMER_FUSED = os.environ.get('SMMD_CRAMER_FUSED', '1') != '0'
+CRAMER_VARIANTS = {'cramer': 0, 'reddit_cramer': 1}
+
+
+def _cramer_fused(*tensors):
+    return CRAMER_FUSED and all(t.is_cuda and t.dtype == torch.float32 for t in tensors)
+
+
+def _same_rows(what, *tensors):
+    if any(t.dim() != 2 or t.shape != tensors[0].shape for t in tensors):
+        raise ValueError('%s: the batches are subtracted row by row and need one [b, d] shape '
+                         '(got %s)' % (what, ', '.join(str(tuple(t.shape)) for t in tensors)))
+
+
+class _CramerHead(torch.autograd.Function):
+    """(d_base, g_loss) of the Cramer head and, from the same launch, the row
+    gradients of the losses in ``want`` (bit 0 d_base, bit 1 g_loss); the
+    backward scales them by the upstream scalars."""
+
+    @staticmethod
+    def forward(ctx, G, G2, X, variant, eps, want):
+        dev = G.device
+        g, g2, x = (t.detach().contiguous() for t in (G, G2, X))
+        b, d = g.shape
+        L = _lib.lib()
+        out = torch.empty(2, device=dev, dtype=torch.float32)
+        sets = [[torch.empty_like(g) for _ in range(3)] if want & bit else [None] * 3
+                for bit in (1, 2)]
+        ws = _lib.workspace('cramer_head', L.smmd_cramer_head_workspace_bytes(b, d), dev)
+        _lib.add_bytes('smmd_cramer_head_fwd', (3 + 3 * bin(want).count('1')) * g.numel() * 4)
+        with _lib.timed('smmd_cramer_head_fwd'):
+            st = L.smmd_cramer_head_fwd(_lib.ptr(g), _lib.ptr(g2), _lib.ptr(x), b, d, variant,
+                                        float(eps), want, _lib.ptr(out),
+                                        *[_lib.ptr(t) for t in sets[0] + sets[1]],
+                                        _lib.ptr(ws), ws.numel(), _lib.stream_handle(dev))
+        _lib.check(st, 'smmd_cramer_head_fwd')
+        ctx.save_for_backward(*[t for t in sets[0] + sets[1] if t is not None])
+        ctx.want = want
+        ctx.set_materialize_grads(False)
+        d_base, g_loss = out.unbind(0)
+        return d_base, g_loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, go_d, go_g):
+        saved = list(ctx.saved_tensors)
+        grads = [None, None, None]
+        for bit, go, name in ((1, go_d, 'd_base'), (2, go_g, 'g_loss')):
+            if not ctx.want & bit:
+                if go is not None:
+                    raise RuntimeError('cramer_head_loss: %s is differentiated but its '
+                                       'gradients were not requested (want=%d)' % (name, ctx.want))
+                continue
+            rows, saved = saved[:3], saved[3:]
+            if go is None:
+                continue
+            for k in range(3):
+                if ctx.needs_input_grad[k]:
+                    t = go * rows[k]
+                    grads[k] = t if grads[k] is None else grads[k] + t
+        return (*grads, None, None, None)
+
+
+def cramer_head_loss(G, G2, images, variant, eps=_eps, want=None):
+    """The Cramer GAN's losses on critic outputs [b, d] of a generated batch,
+    a second generated batch and the real batch, n = safer_norm over a row:
+    'cramer' (cramer.py:85-88): g_loss = mean(-n(G - G2) + n(G - X) + n(G2 - X)),
+    d_base = mean(-n(X - G) + n(X) + n(G2 - G) - n(G2)); 'reddit_cramer'
+    (cramer.py:90-92): g_loss = mean((n(X - G) - n(X)) - (n(G - G2) - n(G))),
+    d_base = -g_loss.  Returns (d_base, g_loss), 0-dim, differentiable once in
+    all three inputs.  ``want``: the losses that will be differentiated (bit 0
+    d_base, bit 1 g_loss; default both when an input requires grad): the
+    kernel writes only those row gradients, and differentiating the other
+    loss raises."""
+    v = CRAMER_VARIANTS.get(variant, variant)
+    if v not in (0, 1):
+        raise ValueError("variant must be 'cramer' or 'reddit_cramer'")
+    _same_rows('cramer_head_loss', G, G2, images)
+    if not _cramer_fused(G, G2, images):
+        def n(t):
+            return safer_norm(t, axis=1, epsilon=eps)
+        if v == 0:
+            g_loss = torch.mean(-n(G - G2) + n(G - images) + n(G2 - images))
+            d_base = torch.mean(-n(images - G) + n(images) + n(G2 - G) - n(G2))
+            return d_base, g_loss
+        g_loss = torch.mean((n(images - G) - n(images)) - (n(G - G2) - n(G)))
+        return -g_loss, g_loss
+    if want is None:
+        want = 3 if any(t.requires_grad for t in (G, G2, images)) else 1
+    if want not in (1, 2, 3):
+        raise ValueError('want must be 1, 2 or 3')
+    return _CramerHead.apply(G, G2, images, v, float(eps), want)
+
+
+class _CramerSeed(torch.autograd.Function):
+    """U = (H - G) / n(H - G) - H / n(H) per row; the backward (one launch)
+    sends an upstream W through the two normalisations."""
+
+    @staticmethod
+    def forward(ctx, H, G, eps):
+        dev = H.device
+        h, g = H.detach().contiguous(), G.detach().contiguous()
+        bs, d = h.shape
+        U = torch.empty_like(h)
+        norms = torch.empty(bs, 2, device=dev, dtype=torch.float64)
+        with _lib.timed('smmd_cramer_seed_fwd'):
+            st = _lib.lib().smmd_cramer_seed_fwd(_lib.ptr(h), _lib.ptr(g), bs, d, float(eps),
+                                                 _lib.ptr(U), _lib.ptr(norms),
+                                                 _lib.stream_handle(dev))
+        _lib.check(st, 'smmd_cramer_seed_fwd')
+        ctx.save_for_backward(h, g, norms)
+        return U
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, W):
+        h, g, norms = ctx.saved_tensors
+        bs, d = h.shape
+        w = W.contiguous().to(torch.float32)
+        gH, gG = torch.empty_like(h), torch.empty_like(h)
+        with _lib.timed('smmd_cramer_seed_bwd'):
+            st = _lib.lib().smmd_cramer_seed_bwd(_lib.ptr(h), _lib.ptr(g), _lib.ptr(norms),
+                                                 _lib.ptr(w), bs, d, _lib.ptr(gH), _lib.ptr(gG),
+                                                 _lib.stream_handle(h.device))
+        _lib.check(st, 'smmd_cramer_seed_bwd')
+        return gH, gG, None
+
+
+def cramer_seed(H, G, eps=_eps):
+    """The seed of the Cramer penalty, U [bs, d] = d sum_i(n(H_i - G_i) -
+    n(H_i)) / dH for critic outputs H of the interpolates and G of the
+    generated batch's first bs rows (cramer.py:81, :88, :96: the grad_outputs
+    of tf.gradients(to_penalize, x_hat_data)).  It depends on the critic, so
+    it is differentiable once in H and G (the penalty's gradient reaches the
+    critic through it)."""
+    _same_rows('cramer_seed', H, G)
+    if not _cramer_fused(H, G):
+        a = H - G
+        return (a / safer_norm(a, axis=1, keep_dims=True, epsilon=eps)
+                - H / safer_norm(H, axis=1, keep_dims=True, epsilon=eps))
+    return _CramerSeed.apply(H, G, float(eps))

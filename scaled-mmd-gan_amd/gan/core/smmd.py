@@ -73,7 +73,9 @@ class SWGAN(MMD_GAN):
 
 
 def get_model(name):
-    """Model dispatch of gan/main.py:139-152 (cramer is outside this build)."""
+    """Model dispatch of gan/main.py:139-152 for the classes that take two
+    critic outputs; the Cramer pair (main.py:145-146) is resolved by gan/main.py
+    itself to gan.core.cramer.Cramer_GAN."""
     if name == 'mmd':
         return MMD_GAN
     if name == 'smmd':
@@ -87,7 +89,8 @@ def get_model(name):
         from .wgan_gp import WGAN_GP
         return WGAN_GP
     if name == 'cramer':
-        raise NotImplementedError('model %r is outside this build (SURVEY.md section 2)' % name)
+        raise NotImplementedError('model %r is not dispatched here: it is '
+                                  'gan.core.cramer.Cramer_GAN (gan/main.py resolve_model)' % name)
     raise ValueError('unknown model {}'.format(name))
 
 

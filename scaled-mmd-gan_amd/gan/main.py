@@ -280,11 +280,20 @@ def main(argv=None):
             dist.destroy_process_group()
 
 
+def resolve_model(name):
+    """gan/main.py:139-152: the Cramer pair is one class told apart by
+    config.model (main.py:145-146); every other name is get_model's."""
+    if name in ('cramer', 'reddit_cramer'):
+        from gan.core.cramer import Cramer_GAN
+        return Cramer_GAN
+    from gan.core.smmd import get_model
+    return get_model(name)
+
+
 def _train(flags, dev, world, rank, size, c_dim):
     import torch
     import torch.distributed as dist
-    from gan.core.smmd import get_model
-    Model = get_model(flags.model)
+    Model = resolve_model(flags.model)
     torch.manual_seed(rank)
     gan = Model(flags, device=dev, process_group=dist.group.WORLD if world > 1 else None,
                 dp_mode=flags.dp_mode, output_size=size, c_dim=c_dim)
