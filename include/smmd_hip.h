@@ -1044,6 +1044,52 @@ smmd_status smmd_conv5s2_wgrad_acc(const float *gy, const float *x, float *gw, i
                                    void *ws, size_t ws_bytes, smmd_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * 5x5 stride-2 convolutions with a thin side (csrc/smmd_conv5s2_thin.hip): the
+ * DCGAN critics' first layer Conv2d(3, dim, 5, 2) and the DCGAN generators'
+ * last layer Deconv2d(dim, 3, 5, 2), on the f32 MFMA, fp32 NCHW.  ct = the thin
+ * channel count (1..4), cw = the wide one (a multiple of 16); the thin tensor
+ * is [n, ct, h, w], the wide one [n, cw, ho, wo], wgt [cw, ct, 5, 5] in every
+ * entry (the critic layer's [cout, cin, 5, 5] and Deconv2d's [cin, cout, 5,
+ * 5]: no transposed copy).  Tap (kh, kw) of wide pixel (oh, ow) touches thin
+ * pixel (2 oh + kh - pt, 2 ow + kw - pl), zero outside the image; pt, pl in
+ * 0..2, ho and wo stated by the caller (TF SAME on an even image: pt = pl = 1,
+ * ho = h / 2).  smmd_conv5s2_thin_supported holds the channel rules, the
+ * padding range, the tap reach (h - 2 <= 2 ho + 2 - pt <= h + 1, w likewise),
+ * every tensor under 2^29 floats and wo <= 256 (<= 81 at ct = 4: the LDS
+ * stages).  Deterministic: fixed-order sums, no atomics; every output element
+ * is written.
+ *
+ * smmd_conv5s2_thin: y [n, cw, ho, wo] = conv(x, wgt) + bias [cw] (may be NULL).
+ * smmd_conv5s2_thin_t: y [n, ct, h, w] = sum over cw and taps of wgt g + bias
+ *   [ct] (may be NULL): the transposed convolution (the critic layer's input
+ *   gradient, the generator layer's forward).
+ * smmd_conv5s2_thin_wgrad: gw [cw, ct, 5, 5] = sum over n, oh, ow of g x; the
+ *   workgroups' partials (smmd_conv5s2_thin_wgrad_workspace_bytes, 16-byte
+ *   aligned like gw) are added in order.  _acc: gw += dW.
+ * ------------------------------------------------------------------------- */
+int smmd_conv5s2_thin_supported(int n, int ct, int cw, int h, int w, int ho, int wo, int pt,
+                                int pl);
+
+smmd_status smmd_conv5s2_thin(const float *x, const float *wgt, const float *bias, float *y, int n,
+                              int ct, int cw, int h, int w, int ho, int wo, int pt, int pl,
+                              smmd_stream_t stream);
+
+smmd_status smmd_conv5s2_thin_t(const float *g, const float *wgt, const float *bias, float *y,
+                                int n, int ct, int cw, int h, int w, int ho, int wo, int pt, int pl,
+                                smmd_stream_t stream);
+
+size_t smmd_conv5s2_thin_wgrad_workspace_bytes(int n, int ct, int cw, int h, int w, int ho, int wo,
+                                               int pt, int pl);
+
+smmd_status smmd_conv5s2_thin_wgrad(const float *g, const float *x, float *gw, int n, int ct,
+                                    int cw, int h, int w, int ho, int wo, int pt, int pl, void *ws,
+                                    size_t ws_bytes, smmd_stream_t stream);
+
+smmd_status smmd_conv5s2_thin_wgrad_acc(const float *g, const float *x, float *gw, int n, int ct,
+                                        int cw, int h, int w, int ho, int wo, int pt, int pl,
+                                        void *ws, size_t ws_bytes, smmd_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * The loss side of the GAN and WGAN-GP baselines (gan/core/gan.py,
  * gan/core/wgan_gp.py).  fp32, one launch each, fixed-order reductions (no
  * float atomics: two runs give the same bits).

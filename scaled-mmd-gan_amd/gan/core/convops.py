@@ -810,8 +810,8 @@ _K5_FASTER = {('dx', 128, 256, 19, 19)}
 def _is_k5s2(x, w, stride, padding, direction='fwd'):
     """conv(x, w [co, ci, 5, 5], stride 2, padding (pt, pl)) -- direction
     'fwd', 'dx' or 'wgrad' of it -- on smmd_conv5s2*: NCHW fp32 contiguous
-    device tensors, ci and co % 64 == 0 (the 3-channel first layer stays on
-    MIOpen), and a shape measured faster there unless CONV5_ALL."""
+    device tensors, ci and co % 64 == 0 (the 3-channel first layer has
+    _is_thin5), and a shape measured faster there unless CONV5_ALL."""
     if not (CONV5 and w.dim() == 4 and tuple(w.shape[2:]) == (5, 5) and x.dim() == 4
             and x.is_cuda and x.dtype == torch.float32 and w.dtype == torch.float32
             and x.is_contiguous() and w.is_contiguous() and w.data_ptr() % 16 == 0
@@ -921,6 +921,186 @@ def _k5s2_wgrad(gy, x, padding, into=None):
     return gw
 
 
+# ---------------------------------------------------------------------------
+# 5x5 stride-2 convolutions with a thin side (<= 4 channels): the DCGAN
+# critics' first layer and the DCGAN generators' last (snops.Deconv2d) on
+# smmd_conv5s2_thin* (csrc/smmd_conv5s2_thin.hip; SMMD_THIN5=0: MIOpen for
+# them).  dims = (N, ct, cw, H, W, Ho, Wo, pt, pl): thin tensor [N, ct, H, W],
+# wide tensor [N, cw, Ho, Wo], weight [cw, ct, 5, 5].
+# ---------------------------------------------------------------------------
+THIN5 = os.environ.get('SMMD_THIN5', '1') != '0'
+# SMMD_THIN5_ALL=1: every shape the kernels take, not only the measured ones
+# below (the A/B tool and the kernels' tests)
+THIN5_ALL = os.environ.get('SMMD_THIN5_ALL', '0') == '1'
+# (entry, ct, cw, H, W) at batch >= 64 where the library beat MIOpen by more
+# than the run-to-run spread (tools/thin5_ab.py, profiles/thin5/); entry is
+# 'conv' (thin in), 'convt' (thin out) or 'wgrad'.  Listed: the entries that
+# won at batch 64 AND 128; the rest (every weight gradient, the transposed conv
+# from 32 x 32 up, the 64 -> 3 layers' input gradient from 64 x 64 up) stays on
+# MIOpen.
+_THIN5_FASTER = {('conv', 3, 64, 35, 35), ('conv', 3, 64, 67, 67), ('conv', 3, 64, 163, 163),
+                 ('conv', 3, 64, 32, 32), ('convt', 3, 64, 35, 35), ('convt', 3, 64, 32, 32)}
+
+
+def _pair(v):
+    return tuple(v) if isinstance(v, (list, tuple)) else (v, v)
+
+
+def _thin5_routed(entry, d):
+    return THIN5_ALL or (d[0] >= 64 and (entry, d[1], d[2], d[3], d[4]) in _THIN5_FASTER)
+
+
+def _thin5_dims(xshape, w, padding):
+    """The kernels' shape arguments of conv(x [xshape], w [cw, ct, 5, 5],
+    stride 2, padding)."""
+    pt, pl = (int(v) for v in _pair(padding))
+    N, ci, H, W = xshape
+    return (N, ci, w.shape[0], H, W, (H + 2 * pt - 5) // 2 + 1, (W + 2 * pl - 5) // 2 + 1, pt, pl)
+
+
+def _is_thin5(x, w, stride, padding, direction='fwd'):
+    """conv(x, w [co, ci, 5, 5], stride 2, padding (pt, pl)) with ci <= 4 --
+    direction 'fwd', 'dx' or 'wgrad' of it -- on smmd_conv5s2_thin*: NCHW fp32
+    contiguous device tensors, a shape the library takes, and one measured
+    faster there unless THIN5_ALL."""
+    if not (THIN5 and w.dim() == 4 and tuple(w.shape[2:]) == (5, 5) and x.dim() == 4
+            and x.is_cuda and x.dtype == torch.float32 and w.dtype == torch.float32
+            and x.is_contiguous() and w.is_contiguous() and x.shape[1] == w.shape[1]
+            and w.shape[1] <= 4 and _pair(stride) == (2, 2)):
+        return False
+    from . import _lib
+    d = _thin5_dims(x.shape, w, padding)
+    if d[5] < 1 or d[6] < 1 or not _lib.lib().smmd_conv5s2_thin_supported(*d):
+        return False
+    return _thin5_routed({'fwd': 'conv', 'dx': 'convt', 'wgrad': 'wgrad'}[direction], d)
+
+
+def _thin5_conv(x, w, b, d):
+    """smmd_conv5s2_thin: y [N, cw, Ho, Wo] = conv(x [N, ct, H, W], w) + b."""
+    from . import _lib
+    if b is not None:
+        b = b.contiguous()
+    _lib.require_cuda(x, w, b)
+    N, ct, cw, H, W, Ho, Wo = d[:7]
+    assert tuple(x.shape) == (N, ct, H, W) and x.is_contiguous() and w.is_contiguous()
+    y = torch.empty((N, cw, Ho, Wo), dtype=x.dtype, device=x.device)
+    _lib.add_bytes('smmd_conv5s2_thin', (x.numel() + y.numel() + w.numel()) * 4)
+    _lib.add_flops('smmd_conv5s2_thin', 2 * 25 * N * Ho * Wo * ct * cw)
+    with _lib.timed('smmd_conv5s2_thin'):
+        st = _lib.lib().smmd_conv5s2_thin(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(y), *d,
+                                          _lib.stream_handle(x.device))
+    _lib.check(st, 'smmd_conv5s2_thin')
+    return y
+
+
+def _thin5_convt(g, w, b, d):
+    """smmd_conv5s2_thin_t: y [N, ct, H, W] = the transposed conv of g [N, cw,
+    Ho, Wo] (+ b [ct]), every element written."""
+    from . import _lib
+    if b is not None:
+        b = b.contiguous()
+    _lib.require_cuda(g, w, b)
+    N, ct, cw, H, W, Ho, Wo = d[:7]
+    assert tuple(g.shape) == (N, cw, Ho, Wo) and g.is_contiguous() and w.is_contiguous()
+    y = torch.empty((N, ct, H, W), dtype=g.dtype, device=g.device)
+    _lib.add_bytes('smmd_conv5s2_thin_t', (g.numel() + y.numel() + w.numel()) * 4)
+    _lib.add_flops('smmd_conv5s2_thin_t', 2 * 25 * N * Ho * Wo * ct * cw)
+    with _lib.timed('smmd_conv5s2_thin_t'):
+        st = _lib.lib().smmd_conv5s2_thin_t(_lib.ptr(g), _lib.ptr(w), _lib.ptr(b), _lib.ptr(y),
+                                            *d, _lib.stream_handle(g.device))
+    _lib.check(st, 'smmd_conv5s2_thin_t')
+    return y
+
+
+def _thin5_wgrad(g, x, d, into=None):
+    """smmd_conv5s2_thin_wgrad: gw [cw, ct, 5, 5] from the wide g [N, cw, Ho,
+    Wo] and the thin x [N, ct, H, W] (into: added to it)."""
+    from . import _lib
+    _lib.require_cuda(g, x)
+    N, ct, cw, H, W, Ho, Wo = d[:7]
+    assert tuple(g.shape) == (N, cw, Ho, Wo) and g.is_contiguous()
+    assert tuple(x.shape) == (N, ct, H, W) and x.is_contiguous()
+    L = _lib.lib()
+    nb = L.smmd_conv5s2_thin_wgrad_workspace_bytes(*d)
+    ws = _lib.workspace('conv5s2_thin_wgrad', nb, x.device)
+    gw, acc = _gw_out(into, (cw, ct, 5, 5), x)
+    _lib.add_bytes('smmd_conv5s2_thin_wgrad', (x.numel() + g.numel() + gw.numel()) * 4)
+    _lib.add_flops('smmd_conv5s2_thin_wgrad', 2 * 25 * N * Ho * Wo * ct * cw)
+    with _lib.timed('smmd_conv5s2_thin_wgrad'):
+        st = getattr(L, 'smmd_conv5s2_thin_wgrad' + acc)(
+            _lib.ptr(g), _lib.ptr(x), _lib.ptr(gw), *d, _lib.ptr(ws), nb,
+            _lib.stream_handle(x.device))
+    _lib.check(st, 'smmd_conv5s2_thin_wgrad')
+    return gw
+
+
+def _convt5_dims(x, w):
+    """conv_transpose5_thin's shape arguments: x [N, cw, Hin, Win] the wide
+    tensor, w [cw, ct, 5, 5], the output [N, ct, 2 Hin, 2 Win] with TF SAME
+    geometry (one zero row before, two after)."""
+    N, cw, Ho, Wo = x.shape
+    return (N, w.shape[1], cw, 2 * Ho, 2 * Wo, Ho, Wo, 1, 1)
+
+
+def convt5_thin_applicable(x, w):
+    """True when conv_transpose2d(x, w [cin, cout <= 4, 5, 5], stride 2,
+    padding 1) cropped to twice the input runs on the thin kernels."""
+    if not (THIN5 and w.dim() == 4 and tuple(w.shape[2:]) == (5, 5) and w.shape[1] <= 4
+            and x.dim() == 4 and x.is_cuda and x.dtype == torch.float32
+            and w.dtype == torch.float32 and x.is_contiguous() and x.shape[1] == w.shape[0]):
+        return False
+    from . import _lib
+    d = _convt5_dims(x, w)
+    return bool(_lib.lib().smmd_conv5s2_thin_supported(*d)) and _thin5_routed('convt', d)
+
+
+class _ConvT5Thin(torch.autograd.Function):
+    """conv_transpose2d(x, w [cin, cout <= 4, 5, 5], b, stride 2, padding 1)
+    [:, :, :2 Hin, :2 Win] (snops.Deconv2d: the DCGAN generator's last layer) on
+    smmd_conv5s2_thin_t.  Backward: grad_x = the thin-in conv of g, grad_w the
+    thin weight gradient with x and g in swapped roles, grad_b the channel sum
+    (the generator step differentiates it once).  A direction not routed to
+    the library takes aten's kernel for the uncropped transposed conv at the
+    zero-extended g."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        w = materialize(w)
+        ctx.save_for_backward(x, w)
+        ctx.has_b = b is not None
+        return _thin5_convt(x, w.contiguous(), b, _convt5_dims(x, w))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        gy = gy.contiguous()
+        d = _convt5_dims(x, w)
+        gx = gw = gb = None
+        lx = ctx.needs_input_grad[0] and _thin5_routed('conv', d)
+        lw = ctx.needs_input_grad[1] and _thin5_routed('wgrad', d)
+        if lx:
+            gx = _thin5_conv(gy, w.contiguous(), None, d)
+        if lw:
+            gw = _thin5_wgrad(x, gy, d)
+        need_x, need_w = ctx.needs_input_grad[0] and not lx, ctx.needs_input_grad[1] and not lw
+        if need_x or need_w:
+            ax, aw, _ = _aten.convolution_backward(F.pad(gy, (0, 1, 0, 1)), x, w, None, [2, 2],
+                                                   [1, 1], [1, 1], True, [0, 0], 1,
+                                                   [need_x, need_w, False])
+            gx = ax if need_x else gx
+            gw = aw if need_w else gw
+        if ctx.has_b and ctx.needs_input_grad[2]:
+            gb = bias_grad(gy)
+        return gx, gw, gb
+
+
+def conv_transpose5_thin(x, w, b=None):
+    """F.conv_transpose2d(x, w, b, stride=2, padding=1)[:, :, :2 Hin, :2 Win]
+    on the thin 5x5 kernels (convt5_thin_applicable says when)."""
+    return _ConvT5Thin.apply(x, w, b)
+
+
 def _is_thin(x, w, stride, padding):
     return thin_applicable(x, w.shape[1], w.shape[0], w.shape[2], stride, padding) \
         and w.shape[2] == w.shape[3]
@@ -950,6 +1130,8 @@ def _fwd(x, w, b, stride, padding, ymask=None, into=None):
         y = _c1_fwd(x, w, b)
         if y is not None:
             return y
+    if _is_thin5(x, w, stride, padding):
+        return _thin5_conv(x, materialize(w), b, _thin5_dims(x.shape, w, padding))
     if _is_k5s2(x, w, stride, padding):
         return _k5s2_conv(x, materialize(w), b, padding)
     return F.conv2d(x, materialize(w), b, stride, padding)
@@ -1009,6 +1191,22 @@ def _bwd_core(gy, x, w, stride, padding, mask, xmask, into=None):
             gw = aw if need_w else gw
         return gx, gw, False
     k5 = gy.is_contiguous() and gy.dtype == torch.float32
+    t5x = k5 and mask[0] and _is_thin5(x, w, stride, padding, 'dx')
+    t5w = k5 and mask[1] and _is_thin5(x, w, stride, padding, 'wgrad')
+    if t5x or t5w:
+        d = _thin5_dims(x.shape, w, padding)
+        gx = _thin5_convt(gy, materialize(w), None, d) if t5x else None
+        gw = _thin5_wgrad(gy, x, d, into) if t5w else None
+        # the other output from aten ALONE (the 1x1 branch's rule: a gw the
+        # *_wgrad_acc kernel added into `into` must not be formed twice)
+        need_x, need_w = mask[0] and not t5x, mask[1] and not t5w
+        if need_x or need_w:
+            ax, aw, _ = _aten.convolution_backward(gy, x, materialize(w), None, stride, padding,
+                                                   [1, 1], False, [0, 0], 1,
+                                                   [need_x, need_w, False])
+            gx = ax if need_x else gx
+            gw = aw if need_w else gw
+        return gx, gw, False
     k5x = k5 and mask[0] and _is_k5s2(x, w, stride, padding, 'dx')
     k5w = k5 and mask[1] and _is_k5s2(x, w, stride, padding, 'wgrad')
     if k5x or k5w:
