@@ -1180,6 +1180,63 @@ smmd_status smmd_cramer_seed_bwd(const float *H, const float *G, const double *n
                                  smmd_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * The loss side of the Sobolev GAN (gan/core/sobolevgan_gp.py).  fp32 in and
+ * out, one launch each, fixed-order reductions with the squares formed and
+ * summed in double (no float atomics: two runs give the same bits).
+ *
+ * smmd_sobolev_fwd: g_real [b_real, per], g_fake [b_fake, per], the critic's
+ *   input gradients at the real and the generated batch, dense in either
+ *   memory format (only the element set matters: each is walked flat, as
+ *   float4 when its base is 16-byte aligned); d_real [b_real], d_fake
+ *   [b_fake] the critic outputs; lam a device scalar, rho >= 0.  With
+ *   e_r = sum(g_real^2) / b_real, e_f = sum(g_fake^2) / b_fake
+ *   (sobolevgan_gp.py:19-20) and c = e_r / 2 + e_f / 2 - 1 (:22):
+ *     out[0] = mean(d_fake) - mean(d_real) + lam c + rho c^2 / 2   (:29, :40)
+ *     out[1] = -mean(d_fake)                                        (:30)
+ *     out[2] = c
+ *     out[3] = lam + rho c: d out[0] / d c, and the next multiplier (:42)
+ *     out[4] = e_r,  out[5] = e_f
+ *   all formed in double from the double sums and rounded once.  Workspace
+ *   from smmd_sobolev_workspace_bytes (0 for sizes out of range), zero at first
+ *   use (the arrival ticket); the call leaves it at rest.
+ * smmd_sobolev_bwd: for an upstream go (device scalar) of out[0], with mult =
+ *   fwd_out[3] read on the device: dg_real = go mult / b_real g_real, dg_fake =
+ *   go mult / b_fake g_fake, each in its input's layout; dd_real[i] =
+ *   -go / b_real, dd_fake[i] = go / b_fake.
+ * smmd_decay_fwd: out[0] = sum_s coef[s] sum_{i in segment s} flat[i]^2 over a
+ *   flat buffer of n floats; segment s is [offsets[s], offsets[s + 1]), the
+ *   nseg + 1 offsets (ascending, within [0, n], any alignment) and the nseg
+ *   coefficients both on the device.  Replaces sobolevgan_gp.py:32-37, :41.
+ *   The table's VALUES are not checked (they live on the device): a table that
+ *   is not ascending gives wrong sums, never an access outside flat.
+ *   Workspace from smmd_decay_workspace_bytes, zero at first use.
+ * smmd_decay_bwd: dflat[i] = go 2 coef[s] flat[i] for i in segment s, and 0
+ *   for every other i in [0, n) and inside a segment whose coefficient is 0
+ *   (written without reading flat: the way to leave a hole in the table).
+ * ------------------------------------------------------------------------- */
+size_t smmd_sobolev_workspace_bytes(int b_real, int b_fake, int64_t per);
+
+smmd_status smmd_sobolev_fwd(const float *g_real, const float *g_fake, const float *d_real,
+                             const float *d_fake, int b_real, int b_fake, int64_t per,
+                             const float *lam, float rho, float *out, void *ws, size_t ws_bytes,
+                             smmd_stream_t stream);
+
+smmd_status smmd_sobolev_bwd(const float *g_real, const float *g_fake, int b_real, int b_fake,
+                             int64_t per, const float *fwd_out, const float *go, float *dg_real,
+                             float *dg_fake, float *dd_real, float *dd_fake,
+                             smmd_stream_t stream);
+
+size_t smmd_decay_workspace_bytes(int64_t n);
+
+smmd_status smmd_decay_fwd(const float *flat, int64_t n, const int64_t *offsets,
+                           const float *coefs, int nseg, float *out, void *ws, size_t ws_bytes,
+                           smmd_stream_t stream);
+
+smmd_status smmd_decay_bwd(const float *flat, int64_t n, const int64_t *offsets,
+                           const float *coefs, int nseg, const float *go, float *dflat,
+                           smmd_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * FID scoring: the moments of gathered code rows (gan/compute_scores.py:193-197,
  * part.mean(axis=0) and np.cov(part, rowvar=False) for part = codes[index]).
  *

@@ -234,6 +234,12 @@ _SIGS = {
                                   _SZ, _P]),
     'smmd_cramer_seed_fwd': (_I, [_P, _P, _I, _I, _F, _P, _P, _P]),
     'smmd_cramer_seed_bwd': (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P]),
+    'smmd_sobolev_workspace_bytes': (_SZ, [_I, _I, _I64]),
+    'smmd_sobolev_fwd': (_I, [_P, _P, _P, _P, _I, _I, _I64, _P, _F, _P, _P, _SZ, _P]),
+    'smmd_sobolev_bwd': (_I, [_P, _P, _I, _I, _I64, _P, _P, _P, _P, _P, _P, _P]),
+    'smmd_decay_workspace_bytes': (_SZ, [_I64]),
+    'smmd_decay_fwd': (_I, [_P, _I64, _P, _P, _I, _P, _P, _SZ, _P]),
+    'smmd_decay_bwd': (_I, [_P, _I64, _P, _P, _I, _P, _P, _P]),
     'smmd_code_moments_workspace_bytes': (_SZ, [_I, _I]),
     'smmd_code_moments': (_I, [_P, _I, _I, _P, _I, _P, _P, _P, _SZ, _P]),
 }

@@ -13,6 +13,9 @@
 * ``cramer_head_loss`` / ``cramer_seed``: the loss side of the Cramer GAN
   (gan/core/cramer.py:81-96): the energy-distance head with its row gradients
   in one launch, the penalty's seed and the seed's backward in one each.
+* ``sobolev_head_loss`` / ``weight_decay``: the loss side of the Sobolev GAN
+  (gan/core/sobolevgan_gp.py:16-42): the constraint head and the decay over the
+  flat parameter buffer, one launch forward and one backward each.
 """
 from __future__ import annotations
 
@@ -617,3 +620,181 @@ def cramer_seed(H, G, eps=_eps):
         return (a / safer_norm(a, axis=1, keep_dims=True, epsilon=eps)
                 - H / safer_norm(H, axis=1, keep_dims=True, epsilon=eps))
     return _CramerSeed.apply(H, G, float(eps))
+
+
+# ---------------------------------------------------------------------------
+# the loss side of the Sobolev GAN (csrc/smmd_sobolev.hip): the critic update's
+# whole head (both energies, the constraint, the augmented-Lagrangian term, the
+# next multiplier) in one launch forward and one backward, and the weight decay
+# over the optimizer's flat parameter buffer in one launch each way.
+# SMMD_SOBOLEV_FUSED=0 routes both through plain tensor ops (A/B); CPU or
+# non-fp32 tensors take that path too, so the model also builds without a GPU.
+# ---------------------------------------------------------------------------
+SOBOLEV_FUSED = os.environ.get('SMMD_SOBOLEV_FUSED', '1') != '0'
+
+
+def _sobolev_fused(*tensors):
+    return SOBOLEV_FUSED and all(t.is_cuda and t.dtype == torch.float32 for t in tensors)
+
+
+def _dense(t):
+    """t when it is dense in either memory format, else a contiguous copy."""
+    return t if t.is_contiguous() or _is_channels_last(t) else t.contiguous()
+
+
+class _SobolevHead(torch.autograd.Function):
+    """(d_base, g_loss, c, mult) in one launch; the backward (one launch)
+    reads mult from the saved outputs on the device."""
+
+    @staticmethod
+    def forward(ctx, d_real, d_fake, g_real, g_fake, lam, rho):
+        dev = g_real.device
+        xr = d_real.detach().reshape(-1).contiguous()
+        xf = d_fake.detach().reshape(-1).contiguous()
+        gr, gf = _dense(g_real.detach()), _dense(g_fake.detach())
+        b_real, b_fake = gr.shape[0], gf.shape[0]
+        per = gr.numel() // b_real
+        L = _lib.lib()
+        out = torch.empty(6, device=dev, dtype=torch.float32)
+        ws = _lib.workspace('sobolev_head', L.smmd_sobolev_workspace_bytes(b_real, b_fake, per),
+                            dev)
+        _lib.add_bytes('smmd_sobolev_fwd', (gr.numel() + gf.numel()) * 4)
+        with _lib.timed('smmd_sobolev_fwd'):
+            st = L.smmd_sobolev_fwd(_lib.ptr(gr), _lib.ptr(gf), _lib.ptr(xr), _lib.ptr(xf), b_real,
+                                    b_fake, per, _lib.ptr(lam), float(rho), _lib.ptr(out),
+                                    _lib.ptr(ws), ws.numel(), _lib.stream_handle(dev))
+        _lib.check(st, 'smmd_sobolev_fwd')
+        ctx.save_for_backward(gr, gf, out)
+        ctx.cfg = (b_real, b_fake, per, d_real.shape, d_fake.shape)
+        d_base, g_loss, c, mult = out[:4].unbind(0)
+        ctx.mark_non_differentiable(g_loss, c, mult)
+        return d_base, g_loss, c, mult
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, go, *unused):
+        gr, gf, out = ctx.saved_tensors
+        b_real, b_fake, per, sr, sf = ctx.cfg
+        dev = gr.device
+        go = go.reshape(1).contiguous().to(torch.float32)
+        dgr, dgf = torch.empty_like(gr), torch.empty_like(gf)      # the inputs' strides (dense)
+        ddr = torch.empty(b_real, device=dev, dtype=torch.float32)
+        ddf = torch.empty(b_fake, device=dev, dtype=torch.float32)
+        _lib.add_bytes('smmd_sobolev_bwd', 2 * (gr.numel() + gf.numel()) * 4)
+        with _lib.timed('smmd_sobolev_bwd'):
+            st = _lib.lib().smmd_sobolev_bwd(_lib.ptr(gr), _lib.ptr(gf), b_real, b_fake, per,
+                                             _lib.ptr(out), _lib.ptr(go), _lib.ptr(dgr),
+                                             _lib.ptr(dgf), _lib.ptr(ddr), _lib.ptr(ddf),
+                                             _lib.stream_handle(dev))
+        _lib.check(st, 'smmd_sobolev_bwd')
+        return ddr.view(sr), ddf.view(sf), dgr, dgf, None, None
+
+
+def sobolev_head_loss(d_real, d_fake, g_real, g_fake, lam, rho):
+    """The Sobolev GAN critic loss before the weight decay, on the critic
+    outputs d_real [b_r, 1], d_fake [b_f, 1] and the critic's input gradients
+    g_real = d sum(D(real)) / d real, g_fake = d sum(D(fake)) / d fake (dense,
+    either memory format): with e_r = sum(g_real^2) / b_r, e_f = sum(g_fake^2)
+    / b_f (sobolevgan_gp.py:19-20) and c = e_r / 2 + e_f / 2 - 1 (:22),
+
+        d_base = mean(d_fake) - mean(d_real) + lam c + rho c^2 / 2   (:29, :40)
+        g_loss = -mean(d_fake)                                        (:30)
+        mult   = lam + rho c                                          (:42)
+
+    ``lam``: a one-element tensor (on the device: read there), ``rho`` a host
+    float.  Returns (d_base, g_loss, c, mult), all 0-dim; d_base is
+    differentiable once in the four tensors (the rest of a critic update's
+    chain is the critic's own second-order rule), the other three are values:
+    mult is both d d_base / d c and the next multiplier."""
+    b_real, b_fake = g_real.shape[0], g_fake.shape[0]
+    if (d_real.numel() != b_real or d_fake.numel() != b_fake
+            or g_real.numel() // b_real != g_fake.numel() // b_fake or lam.numel() != 1):
+        raise ValueError('sobolev_head_loss: d_real %s, d_fake %s, g_real %s, g_fake %s, lam %s'
+                         % tuple(tuple(t.shape) for t in (d_real, d_fake, g_real, g_fake, lam)))
+    if not _sobolev_fused(d_real, d_fake, g_real, g_fake, lam):
+        lam = lam.detach().reshape(()).to(g_real.dtype)
+        e_real = (g_real * g_real).sum() / b_real
+        e_fake = (g_fake * g_fake).sum() / b_fake
+        c = 0.5 * e_real + 0.5 * e_fake - 1.0
+        mf = d_fake.mean()
+        d_base = mf - d_real.mean() + lam * c + 0.5 * rho * c * c
+        return d_base, (-mf).detach(), c.detach(), (lam + rho * c).detach()
+    return _SobolevHead.apply(d_real, d_fake, g_real, g_fake, lam.detach(), float(rho))
+
+
+def _flat_offset(p, flat):
+    """Element offset of parameter p inside the flat buffer it is a view of."""
+    o, r = divmod(p.data_ptr() - flat.data_ptr(), flat.element_size())
+    if r or o < 0 or o + p.numel() > flat.numel() or p.dtype != flat.dtype:
+        raise ValueError('weight_decay: a parameter %s is not a view of the flat buffer'
+                         % (tuple(p.shape),))
+    return o
+
+
+class _WeightDecay(torch.autograd.Function):
+    """sum_s coef_s sum_{i in s} flat_i^2 in one launch; the backward writes
+    one dflat (one launch) and hands every parameter its view of it."""
+
+    @staticmethod
+    def forward(ctx, flat, offsets, coefs, *params):
+        dev = flat.device
+        L = _lib.lib()
+        n = flat.numel()
+        out = torch.empty(1, device=dev, dtype=torch.float32)
+        ws = _lib.workspace('decay', L.smmd_decay_workspace_bytes(n), dev)
+        _lib.add_bytes('smmd_decay_fwd', n * 4)
+        with _lib.timed('smmd_decay_fwd'):
+            st = L.smmd_decay_fwd(_lib.ptr(flat), n, _lib.ptr(offsets), _lib.ptr(coefs),
+                                  coefs.numel(), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
+                                  _lib.stream_handle(dev))
+        _lib.check(st, 'smmd_decay_fwd')
+        ctx.save_for_backward(flat, offsets, coefs)
+        ctx.views = [(p.shape, p.stride(), _flat_offset(p, flat)) for p in params]
+        return out.view(())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, go):
+        flat, offsets, coefs = ctx.saved_tensors
+        n = flat.numel()
+        go = go.reshape(1).contiguous().to(torch.float32)
+        dflat = torch.empty_like(flat)
+        _lib.add_bytes('smmd_decay_bwd', 2 * n * 4)
+        with _lib.timed('smmd_decay_bwd'):
+            st = _lib.lib().smmd_decay_bwd(_lib.ptr(flat), n, _lib.ptr(offsets), _lib.ptr(coefs),
+                                           coefs.numel(), _lib.ptr(go), _lib.ptr(dflat),
+                                           _lib.stream_handle(flat.device))
+        _lib.check(st, 'smmd_decay_bwd')
+        return (None, None, None,
+                *[torch.as_strided(dflat, sh, st_, o) for sh, st_, o in ctx.views])
+
+
+def weight_decay(params, flat, offsets, coefs):
+    """sum over segments s of coefs[s] * sum(flat[offsets[s]:offsets[s + 1]]^2)
+    (sobolevgan_gp.py:32-37, :41) for ``params`` that are views of the 1-D
+    buffer ``flat`` (FlatAdam's ``flat_param``): ``offsets`` [nseg + 1] int64
+    ascending element offsets and ``coefs`` [nseg] of flat's dtype, both on
+    flat's device; every parameter lies inside one segment.  A 0-dim tensor,
+    differentiable once with respect to each parameter: 2 coef_s p."""
+    params = list(params)
+    if (flat.dim() != 1 or not flat.is_contiguous() or offsets.dtype != torch.int64
+            or offsets.numel() != coefs.numel() + 1 or coefs.numel() < 1):
+        raise ValueError('weight_decay: flat %s, offsets %s %s, coefs %s'
+                         % (tuple(flat.shape), tuple(offsets.shape), offsets.dtype,
+                            tuple(coefs.shape)))
+    if _sobolev_fused(flat, coefs) and offsets.is_cuda:
+        return _WeightDecay.apply(flat, offsets.contiguous(), coefs.contiguous(), *params)
+    import bisect
+    host = getattr(offsets, '_smmd_host', None)        # (read back once per table)
+    if host is None:
+        host = offsets._smmd_host = (offsets.tolist(), coefs.tolist())
+    offs, cfs = host
+    total = flat.new_zeros(())
+    for p in params:
+        o = _flat_offset(p, flat)
+        s = bisect.bisect_right(offs, o) - 1
+        if not (0 <= s < len(cfs) and o + p.numel() <= offs[s + 1]):
+            raise ValueError('weight_decay: a parameter %s at offset %d lies in no one segment'
+                             % (tuple(p.shape), o))
+        total = total + cfs[s] * (p * p).sum()
+    return total

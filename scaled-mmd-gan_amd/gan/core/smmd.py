@@ -88,6 +88,9 @@ def get_model(name):
     if name == 'wgan_gp':
         from .wgan_gp import WGAN_GP
         return WGAN_GP
+    if name == 'sobolev_gan':
+        from .sobolevgan_gp import SobolevGAN
+        return SobolevGAN
     if name == 'cramer':
         raise NotImplementedError('model %r is not dispatched here: it is '
                                   'gan.core.cramer.Cramer_GAN (gan/main.py resolve_model)' % name)

@@ -282,7 +282,9 @@ def main(argv=None):
 
 def resolve_model(name):
     """gan/main.py:139-152: the Cramer pair is one class told apart by
-    config.model (main.py:145-146); every other name is get_model's."""
+    config.model (main.py:145-146); every other name is get_model's, among
+    them 'sobolev_gan' (gan.core.sobolevgan_gp.SobolevGAN), which the
+    reference's main.py never dispatches to."""
     if name in ('cramer', 'reddit_cramer'):
         from gan.core.cramer import Cramer_GAN
         return Cramer_GAN
