@@ -76,7 +76,10 @@ int smmd_abi_version(void);         /* bumped on any ABI change (2: Gram/poly,
                                        15: smmd_wino4x4s2_conv_acc,
                                        16: smmd_conv1x1_t,
                                        17: smmd_smmd_loss_fwd_gathered,
-                                       smmd_smmd_loss_bwd_ex) */
+                                       smmd_smmd_loss_bwd_ex; added since
+                                       without a bump: smmd_conv5s2t_supported,
+                                       smmd_conv5s2t_workspace_bytes,
+                                       smmd_conv5s2t) */
 const char *smmd_source_hash(void); /* first 16 hex digits of the SHA-256 of the
                                        sources this binary was built from
                                        (csrc .hip and .hpp files in byte order,
@@ -1088,6 +1091,39 @@ smmd_status smmd_conv5s2_thin_wgrad(const float *g, const float *x, float *gw, i
 smmd_status smmd_conv5s2_thin_wgrad_acc(const float *g, const float *x, float *gw, int n, int ct,
                                         int cw, int h, int w, int ho, int wo, int pt, int pl,
                                         void *ws, size_t ws_bytes, smmd_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * The wide 5x5 stride-2 transposed convolutions of the DCGAN generators
+ * (snops.Deconv2d(cin, cout, 5, 2): 512@4 -> 256@8 -> 128@16 -> 64@32 ...) on
+ * the f32 MFMA, fp32 NCHW (csrc/smmd_conv5s2t.hip; additive to ABI 17).
+ * x [n, cin, h, w], wgt [cin, cout, 5, 5] as Deconv2d stores it (no transformed
+ * copy, no filter launch), y [n, cout, 2h, 2w]:
+ *   y[n, co, oh, ow] = bias[co] + sum over ci and the (ih, kh) with
+ *   oh = 2 ih + kh - 1, (iw, kw) likewise, of x[n, ci, ih, iw] wgt[ci, co, kh, kw]
+ * = conv_transpose2d(x, wgt, bias, 2, 1)[:, :, :2h, :2w], the TF SAME geometry.
+ * One workgroup computes all four output parity phases of 64 channels x 64
+ * input-grid pixels from one staged patch of x.
+ *
+ * smmd_conv5s2t_supported: cout % 64 == 0, cin % 4 == 0 (the reduction's chunk),
+ *   x, y and wgt each under 2^29 floats, and the patch of a 64-pixel run of the
+ *   input grid (its rows, a halo row above and below, two more per image
+ *   boundary crossed, w + 2 floats each) within 512 floats: w <= 83 at any h,
+ *   but not a 1 x 1 image.
+ * smmd_conv5s2t: bias [cout] may be NULL.  With few tiles the input channels
+ *   are split over workgroups, by a rule of the shape only; the partial outputs
+ *   (smmd_conv5s2t_workspace_bytes; 0 = no split) are added in slice order.
+ *   wgt, y and the workspace 16-byte aligned.  A NULL x, wgt or y, a misaligned
+ *   pointer and a workspace that is NULL or short give SMMD_EINVAL, a shape
+ *   outside the rule SMMD_EUNSUPPORTED, all before any launch.  Deterministic:
+ *   fixed-order sums, no atomics; every output element is written.
+ * ------------------------------------------------------------------------- */
+int smmd_conv5s2t_supported(int n, int cin, int cout, int h, int w);
+
+size_t smmd_conv5s2t_workspace_bytes(int n, int cin, int cout, int h, int w);
+
+smmd_status smmd_conv5s2t(const float *x, const float *wgt, const float *bias, float *y, int n,
+                          int cin, int cout, int h, int w, void *ws, size_t ws_bytes,
+                          smmd_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * The loss side of the GAN and WGAN-GP baselines (gan/core/gan.py,

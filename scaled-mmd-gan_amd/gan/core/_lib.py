@@ -169,6 +169,9 @@ _SIGS = {
     'smmd_conv5s2_thin_wgrad_workspace_bytes': (_SZ, [_I] * 9),
     'smmd_conv5s2_thin_wgrad': (_I, [_P, _P, _P] + [_I] * 9 + [_P, _SZ, _P]),
     'smmd_conv5s2_thin_wgrad_acc': (_I, [_P, _P, _P] + [_I] * 9 + [_P, _SZ, _P]),
+    'smmd_conv5s2t_supported': (_I, [_I] * 5),
+    'smmd_conv5s2t_workspace_bytes': (_SZ, [_I] * 5),
+    'smmd_conv5s2t': (_I, [_P, _P, _P, _P] + [_I] * 5 + [_P, _SZ, _P]),
     'smmd_channel_sum_workspace_bytes': (_SZ, [_I, _I]),
     'smmd_channel_sum': (_I, [_P, _I, _I, _I, _P, _P, _SZ, _P]),
     'smmd_conv3x3_thin': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),

@@ -836,13 +836,14 @@ def _k5s2_dims(xshape, co, padding):
     return (N, ci, co, H, W, (H + 2 * pt - 5) // 2 + 1, (W + 2 * pl - 5) // 2 + 1, pt, pl)
 
 
-def _k5s2_conv(x, w, b, padding):
-    """conv2d(x, w, b, stride 2, padding) on smmd_conv5s2."""
+def _k5s2_conv(x, w, b, padding, d=None):
+    """conv2d(x, w, b, stride 2, padding) on smmd_conv5s2 (d: the shape
+    arguments where the output size is not the symmetric one)."""
     from . import _lib
     if b is not None:
         b = b.contiguous()
     _lib.require_cuda(x, w, b)
-    d = _k5s2_dims(x.shape, w.shape[0], padding)
+    d = d or _k5s2_dims(x.shape, w.shape[0], padding)
     N, ci, co, H, W, Ho, Wo = d[:7]
     L = _lib.lib()
     y = torch.empty((N, co, Ho, Wo), dtype=x.dtype, device=x.device)
@@ -899,12 +900,12 @@ def _k5s2_dx(gy, w, xshape, padding):
     return gx
 
 
-def _k5s2_wgrad(gy, x, padding, into=None):
+def _k5s2_wgrad(gy, x, padding, into=None, d=None):
     """smmd_conv5s2_wgrad: gw [co, ci, 5, 5] of conv(x, ., stride 2, padding) at
-    gy (into: added to it)."""
+    gy (into: added to it; d: as in _k5s2_conv)."""
     from . import _lib
     _lib.require_cuda(gy, x)
-    d = _k5s2_dims(x.shape, gy.shape[1], padding)
+    d = d or _k5s2_dims(x.shape, gy.shape[1], padding)
     N, ci, co, H, W, Ho, Wo = d[:7]
     assert tuple(gy.shape) == (N, co, Ho, Wo) and gy.is_contiguous()
     L = _lib.lib()
@@ -1099,6 +1100,137 @@ def conv_transpose5_thin(x, w, b=None):
     """F.conv_transpose2d(x, w, b, stride=2, padding=1)[:, :, :2 Hin, :2 Win]
     on the thin 5x5 kernels (convt5_thin_applicable says when)."""
     return _ConvT5Thin.apply(x, w, b)
+
+
+# ---------------------------------------------------------------------------
+# The wide 5x5 stride-2 transposed convolutions of the DCGAN generators
+# (snops.Deconv2d(cin, cout > 4, 5, 2)) on smmd_conv5s2t
+# (csrc/smmd_conv5s2t.hip; SMMD_CONVT5=0: MIOpen for them): all four output
+# parity phases from one staged patch, the weight read as Deconv2d stores it.
+# ---------------------------------------------------------------------------
+CONVT5 = os.environ.get('SMMD_CONVT5', '1') != '0'
+# SMMD_CONVT5_ALL=1: every shape the kernel takes, not only the measured ones
+# below (the A/B tool and the kernel's tests)
+CONVT5_ALL = os.environ.get('SMMD_CONVT5_ALL', '0') == '1'
+# ('fwd', cin, cout, h, w) at batch >= 64 where the library beat MIOpen's
+# transposed conv + crop by more than the run-to-run spread (tools/convt5_ab.py,
+# profiles/convt5/): every wide layer of dcgan at 32 and 64 px and of dcgan5 at
+# 64 px (33-88 us against 55-232).  The backward directions run on smmd_conv5s2
+# / smmd_conv5s2_wgrad and keep those kernels' table (_K5_FASTER, CONV5_ALL).
+_CONVT5_FASTER = {('fwd', 1024, 512, 2, 2), ('fwd', 512, 256, 2, 2), ('fwd', 512, 256, 4, 4),
+                  ('fwd', 256, 128, 4, 4), ('fwd', 256, 128, 8, 8), ('fwd', 128, 64, 8, 8),
+                  ('fwd', 128, 64, 16, 16)}
+
+
+def _convt5(x, w, b):
+    """smmd_conv5s2t: y [N, cout, 2h, 2w] = conv_transpose2d(x [N, cin, h, w],
+    w [cin, cout, 5, 5], b, 2, 1)[:, :, :2h, :2w]."""
+    from . import _lib
+    if b is not None:
+        b = b.contiguous()
+    _lib.require_cuda(x, w, b)
+    N, ci, H, W = x.shape
+    co = w.shape[1]
+    assert w.shape[0] == ci and x.is_contiguous() and w.is_contiguous()
+    L = _lib.lib()
+    d = (N, ci, co, H, W)
+    y = torch.empty((N, co, 2 * H, 2 * W), dtype=x.dtype, device=x.device)
+    nb = L.smmd_conv5s2t_workspace_bytes(*d)
+    ws = _lib.workspace('conv5s2t', nb, x.device) if nb else None
+    _lib.add_bytes('smmd_conv5s2t', (x.numel() + y.numel() + w.numel()) * 4)
+    _lib.add_flops('smmd_conv5s2t', 2 * 25 * N * H * W * ci * co)
+    with _lib.timed('smmd_conv5s2t'):
+        st = L.smmd_conv5s2t(_lib.ptr(x), _lib.ptr(w), _lib.ptr(b), _lib.ptr(y), *d, _lib.ptr(ws),
+                             nb, _lib.stream_handle(x.device))
+    _lib.check(st, 'smmd_conv5s2t')
+    return y
+
+
+def convt5_applicable(x, w):
+    """True when conv_transpose2d(x, w [cin, cout, 5, 5], stride 2, padding 1)
+    cropped to twice the input runs on smmd_conv5s2t: NCHW fp32 contiguous
+    device tensors, a shape the kernel takes, and one measured faster there
+    unless CONVT5_ALL."""
+    if not (CONVT5 and w.dim() == 4 and tuple(w.shape[2:]) == (5, 5) and x.dim() == 4
+            and x.is_cuda and x.dtype == torch.float32 and w.dtype == torch.float32
+            and x.is_contiguous() and w.is_contiguous() and w.data_ptr() % 16 == 0
+            and x.shape[1] == w.shape[0]):
+        return False
+    from . import _lib
+    N, ci, H, W = x.shape
+    if not _lib.lib().smmd_conv5s2t_supported(N, ci, w.shape[1], H, W):
+        return False
+    return CONVT5_ALL or (N >= 64 and ('fwd', ci, w.shape[1], H, W) in _CONVT5_FASTER)
+
+
+def _convt5_bwd_dims(x, w):
+    """The shape arguments of the convolution that maps y's side back to x's:
+    gy [N, cout, 2h, 2w] -> [N, cin, h, w] with w [cin, cout, 5, 5] as its
+    [co, ci, 5, 5], pt = pl = 1 and the output size stated (the last row's
+    taps 2h, 2h + 1 read as zero)."""
+    N, ci, H, W = x.shape
+    return (N, w.shape[1], ci, 2 * H, 2 * W, H, W, 1, 1)
+
+
+def _convt5_bwd_routed(direction, d, w):
+    """direction 'fwd' (smmd_conv5s2) or 'wgrad' (smmd_conv5s2_wgrad) of that
+    convolution on the library: by the table of those kernels."""
+    if not (CONV5 and w.data_ptr() % 16 == 0):
+        return False
+    from . import _lib
+    N, ci, co, H, W = d[:5]
+    # (supported() derives its output size from the input's: H + 1 gives H / 2)
+    if not _lib.lib().smmd_conv5s2_supported(N, ci, co, H + 1, W + 1, 1, 1):
+        return False
+    return CONV5_ALL or (N >= 64 and (direction, ci, co, H, W) in _K5_FASTER)
+
+
+class _ConvT5(torch.autograd.Function):
+    """conv_transpose2d(x, w [cin, cout, 5, 5], b, stride 2, padding 1)
+    [:, :, :2h, :2w] (snops.Deconv2d: the DCGAN generator's wide layers) on
+    smmd_conv5s2t.  Backward (once: the generator is never differentiated
+    twice): grad_x = smmd_conv5s2 of gy with w as that convolution's [co, ci,
+    5, 5], grad_w = smmd_conv5s2_wgrad with x and gy in swapped roles (it lands
+    in the stored layout), grad_b the channel sum.  A direction not routed to
+    the library takes aten's kernel for the uncropped transposed conv at the
+    zero-extended gy."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        w = materialize(w)
+        ctx.save_for_backward(x, w)
+        ctx.has_b = b is not None
+        return _convt5(x, w, b)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        gy = gy.contiguous()
+        d = _convt5_bwd_dims(x, w)
+        gx = gw = gb = None
+        lx = ctx.needs_input_grad[0] and _convt5_bwd_routed('fwd', d, w)
+        lw = ctx.needs_input_grad[1] and _convt5_bwd_routed('wgrad', d, w)
+        if lx:
+            gx = _k5s2_conv(gy, w, None, (1, 1), d)
+        if lw:
+            gw = _k5s2_wgrad(x, gy, (1, 1), None, d)
+        need_x, need_w = ctx.needs_input_grad[0] and not lx, ctx.needs_input_grad[1] and not lw
+        if need_x or need_w:
+            ax, aw, _ = _aten.convolution_backward(F.pad(gy, (0, 1, 0, 1)), x, w, None, [2, 2],
+                                                   [1, 1], [1, 1], True, [0, 0], 1,
+                                                   [need_x, need_w, False])
+            gx = ax if need_x else gx
+            gw = aw if need_w else gw
+        if ctx.has_b and ctx.needs_input_grad[2]:
+            gb = bias_grad(gy)
+        return gx, gw, gb
+
+
+def conv_transpose5(x, w, b=None):
+    """F.conv_transpose2d(x, w, b, stride=2, padding=1)[:, :, :2h, :2w] on
+    smmd_conv5s2t (convt5_applicable says when)."""
+    return _ConvT5.apply(x, w, b)
 
 
 def _is_thin(x, w, stride, padding):

@@ -17,8 +17,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .convops import (conv2d, conv2d_relu, conv_transpose5_thin, convt5_thin_applicable,
-                      thin_applicable)
+from .convops import (conv2d, conv2d_relu, conv_transpose5, conv_transpose5_thin,
+                      convt5_applicable, convt5_thin_applicable, thin_applicable)
 
 
 def same_pad(n_in, k, s):
@@ -131,6 +131,10 @@ class Deconv2d(nn.Module, _SNMixin):
             # the DCGAN generator's dim -> 3 output layer: SAME at stride 2 pads
             # one row before and two after (csrc/smmd_conv5s2_thin.hip)
             return conv_transpose5_thin(x, w, self.bias)
+        if self.k == 5 and self.stride == 2 and self.cout > 4 and convt5_applicable(x, w):
+            # the DCGAN generator's wide layers, same geometry: all four output
+            # parity phases from one staged patch (csrc/smmd_conv5s2t.hip)
+            return conv_transpose5(x, w, self.bias)
         y = F.conv_transpose2d(x, w, self.bias, self.stride, before)
         if y.shape[2] != h or y.shape[3] != wd:
             y = y[:, :, :h, :wd]
