@@ -79,7 +79,9 @@ int smmd_abi_version(void);         /* bumped on any ABI change (2: Gram/poly,
                                        smmd_smmd_loss_bwd_ex; added since
                                        without a bump: smmd_conv5s2t_supported,
                                        smmd_conv5s2t_workspace_bytes,
-                                       smmd_conv5s2t) */
+                                       smmd_conv5s2t,
+                                       smmd_fid_trace_sqrt_workspace_bytes,
+                                       smmd_fid_trace_sqrt) */
 const char *smmd_source_hash(void); /* first 16 hex digits of the SHA-256 of the
                                        sources this binary was built from
                                        (csrc .hip and .hpp files in byte order,
@@ -1301,6 +1303,36 @@ size_t smmd_code_moments_workspace_bytes(int n, int dim);
 smmd_status smmd_code_moments(const float *codes, int n_rows, int dim, const int64_t *index, int n,
                               double *mean, double *cov, void *ws, size_t ws_bytes,
                               smmd_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * FID scoring: the spectral step (gan/compute_scores.py:199-206, the trace of
+ * sqrtm(cov_g cov_r)) on the f64 matrix cores, without eigenvectors.
+ *
+ * smmd_fid_trace_sqrt: cov_g, cov_r [dim, dim] row-major double, symmetric
+ *   positive semi-definite, any dim >= 1.  For a PSD A the coupled
+ *   Newton-Schulz iteration runs on Y0 = A / |A|_F + delta I, Z0 = I:
+ *       T = 1.5 I - 0.5 Z Y;  Y <- Y T;  Z <- T Z        (iters times)
+ *   with full products on v_mfma_f64_16x16x4_f64 and no convergence test (no
+ *   host read inside the call).  Stage 1 takes Y1 = Y(cov_g), stage 2 forms
+ *   M = c1 Y1 cov_r Y1 (c1 = |cov_g|_F), stage 3 takes Y3 = Y(M).
+ *   out4 [4] double = {sqrt(c3) tr Y3 (the trace of sqrt(cov_g cov_r) up to
+ *   the shift), |Y1^2 - Y0|_F of stage 1, |Y3^2 - Y0|_F of stage 3, c3 = |M|_F}.
+ *   delta > 0 is required (rounding leaves eigenvalues of about -1e-16 |A|,
+ *   which the unshifted iteration amplifies); the callers use delta = 1e-14
+ *   and iters = ceil(log_1.5 delta^-1/2) + 12 = 52.
+ *   No floating-point atomics, no counters, every reduction in index order:
+ *   two runs give the same bits, and the workspace (from
+ *   smmd_fid_trace_sqrt_workspace_bytes, 0 for dim < 1; 256 + 3 align256(8
+ *   ceil(dim / 128)^2) + 6 align256(8 dim^2) bytes) needs no particular
+ *   contents on entry.
+ *   SMMD_EINVAL: a NULL matrix or out4, dim < 1, delta <= 0, iters < 1;
+ *   SMMD_EWORKSPACE: a NULL or short workspace.
+ * ------------------------------------------------------------------------- */
+size_t smmd_fid_trace_sqrt_workspace_bytes(int dim);
+
+smmd_status smmd_fid_trace_sqrt(const double *cov_g, const double *cov_r, int dim, double delta,
+                                int iters, double *out4, void *ws, size_t ws_bytes,
+                                smmd_stream_t stream);
 
 #ifdef __cplusplus
 }

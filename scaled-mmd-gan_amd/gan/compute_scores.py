@@ -132,13 +132,15 @@ def _split_moments(codes, w):
     return code_moments(codes, torch.from_numpy(np.asarray(w, dtype=np.int64)))
 
 
-def fid_score(codes_g, codes_r, eps=1e-6, output=sys.stdout, **split_args):
+def fid_score(codes_g, codes_r, eps=1e-6, output=sys.stdout, spectral=None, **split_args):
     """FID per split (:180-208) as a numpy array of ``splits`` scores.  The
     codes go to the device once; each split hands its slice or bootstrap index
     to ``code_moments`` (no gathered copy).  ``eps`` is unused: the eigenvalue
     form of the trace term (``frechet_distance``) is defined on singular
     covariances, so the reference's retry (:200-203) has nothing to do; it is
-    kept for the signature.  ``output`` took the reference's progress bar."""
+    kept for the signature.  ``output`` took the reference's progress bar.
+    ``spectral`` ('host', 'device' or None for ``SMMD_FID_SQRT``) goes to
+    ``frechet_distance``."""
     splits_g = get_splits(codes_g.shape[0], **split_args)
     splits_r = get_splits(codes_r.shape[0], **split_args)
     assert len(splits_g) == len(splits_r)
@@ -150,7 +152,7 @@ def fid_score(codes_g, codes_r, eps=1e-6, output=sys.stdout, **split_args):
     for i, (w_g, w_r) in enumerate(zip(splits_g, splits_r)):
         mn_g, cov_g = _split_moments(G, w_g)
         mn_r, cov_r = _split_moments(R, w_r)
-        scores[i] = frechet_distance(mn_g, cov_g, mn_r, cov_r)
+        scores[i] = frechet_distance(mn_g, cov_g, mn_r, cov_r, spectral=spectral)
     return scores
 
 
@@ -174,6 +176,9 @@ def main(argv=None):
     parser.add_argument('--split-method', choices=['openai', 'bootstrap'], default='bootstrap')
     parser.add_argument('--device', default=None,
                         help="where the moments run: 'cuda' (default where there is one) or 'cpu'")
+    parser.add_argument('--fid-spectral', choices=['host', 'device'], default=None,
+                        help="the FID's spectral step: float64 eigh on the host (default, or "
+                             "what SMMD_FID_SQRT says) or the f64 matrix cores")
     args = parser.parse_args(argv)
     if args.output and os.path.exists(args.output):
         parser.error("Path {} already exists".format(args.output))
@@ -192,7 +197,8 @@ def main(argv=None):
             codes_f, ref_f = _codes(codes, dev), _codes(ref, dev)
         else:
             codes_f, ref_f = codes, ref
-        scores = fid_score(codes_f, ref_f, splits=args.splits, split_method=args.split_method)
+        scores = fid_score(codes_f, ref_f, splits=args.splits, split_method=args.split_method,
+                           spectral=args.fid_spectral)
         print("FID mean:", np.mean(scores))
         print("FID std:", np.std(scores))
         to_save['fid'] = scores

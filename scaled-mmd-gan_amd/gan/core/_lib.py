@@ -82,6 +82,7 @@ _I = ctypes.c_int
 _I64 = ctypes.c_int64
 _F = ctypes.c_float
 _SZ = ctypes.c_size_t
+_D = ctypes.c_double
 
 # name -> (restype, argtypes)
 _SIGS = {
@@ -245,6 +246,8 @@ _SIGS = {
     'smmd_decay_bwd': (_I, [_P, _I64, _P, _P, _I, _P, _P, _P]),
     'smmd_code_moments_workspace_bytes': (_SZ, [_I, _I]),
     'smmd_code_moments': (_I, [_P, _I, _I, _P, _I, _P, _P, _P, _SZ, _P]),
+    'smmd_fid_trace_sqrt_workspace_bytes': (_SZ, [_I]),
+    'smmd_fid_trace_sqrt': (_I, [_P, _P, _I, _D, _I, _P, _P, _SZ, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)

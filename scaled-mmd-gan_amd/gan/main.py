@@ -74,6 +74,9 @@ _FLAGS = [
     # this build: also score the FID each round (the reference always does,
     # scorer.py:95-101; off by default here so existing runs draw and log as before)
     ('compute_fid', False, str2bool),
+    # this build: where the FID's spectral step runs: 'host' (float64 eigh) or
+    # 'device' (smmd_fid_trace_sqrt, the f64 matrix cores)
+    ('fid_spectral', 'host', str),
 ]
 _DOUBLE_DASH = [('use-incomplete-cho', True, str2bool), ('incho-eta', 1e-3, float),
                 ('incho-max-steps', 1000, int)]
@@ -224,7 +227,8 @@ def make_scorer(flags, pipe, dev, size):
             np.save(path, codes)
         except OSError:
             pass
-    return Scorer(codes, lr_scheduler=flags.MMD_lr_scheduler, fid=flags.compute_fid), feat
+    return Scorer(codes, lr_scheduler=flags.MMD_lr_scheduler, fid=flags.compute_fid,
+                  fid_spectral=getattr(flags, 'fid_spectral', 'host')), feat
 
 
 def make_pipeline(flags, size, c_dim, dev, rank=0, world=1):

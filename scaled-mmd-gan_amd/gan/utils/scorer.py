@@ -30,7 +30,9 @@ def _norm_cdf(x):
 
 class Scorer:
     def __init__(self, train_codes, lr_scheduler=True, n_subsets=10, subset_size=1000,
-                 three_sample_size=2048, fid=False, fid_splits=3):
+                 three_sample_size=2048, fid=False, fid_splits=3, fid_spectral='host'):
+        if fid_spectral not in ('host', 'device'):
+            raise ValueError("fid_spectral must be 'host' or 'device' (got %r)" % (fid_spectral,))
         self.train_codes = np.asarray(train_codes, dtype=np.float32)
         self.lr_scheduler = lr_scheduler
         self.n_subsets = n_subsets
@@ -38,6 +40,7 @@ class Scorer:
         self.bs = three_sample_size
         self.fid = fid
         self.fid_splits = fid_splits
+        self.fid_spectral = fid_spectral
         self.output = []
         self.three_sample = []
         self.three_sample_chances = 0
@@ -48,8 +51,10 @@ class Scorer:
             return None
         output = {}
         if self.fid:
+            # 'host' is fid_score's default: the call stays as it was
+            spectral = {'spectral': 'device'} if self.fid_spectral == 'device' else {}
             output['fid'] = fid = cs.fid_score(codes, self.train_codes, split_method='bootstrap',
-                                               splits=self.fid_splits)
+                                               splits=self.fid_splits, **spectral)
             timer = getattr(gan, 'timer', None)
             if timer is not None:
                 timer(step, "FID mean (std): %f (%f)" % (fid.mean(), fid.std()))

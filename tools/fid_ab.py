@@ -129,10 +129,10 @@ def main():
     eig = []
     inner = cs.frechet_distance
 
-    def timed_fd(*a):
+    def timed_fd(*a, **k):
         torch.cuda.synchronize()
         t = time.perf_counter()
-        r = inner(*a)
+        r = inner(*a, **k)
         eig.append(time.perf_counter() - t)
         return r
     cs.frechet_distance = timed_fd
